@@ -7,15 +7,22 @@ monotone limiter) on a synthetic x1.163842 JW baroclinic-wave state, 56 levels,
 fp64.  value = nCells * nVertLevels / t_dt (cell-updates per second of the whole mesh;
 N GPUs split the mesh into N blocks with halos -- strong scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 
-Also reported:
+A plain run sets up, warms up, times the K steps and prints the result line (with several ranks
+the host-side plan preflight still runs first: it is what keeps a mispaired exchange from hanging).
+--dump-outputs DIR writes the prognostic state the last timed step left as DIR/<field>.npy.
+
+With --full also measured, checked and reported:
   roofline      acoustic sub-step (atm_advance_acoustic_step + atm_divergence_damping_3d),
                 algorithmic bytes B_ac / measured time (HIP events on the
                 dycore's stream) vs the 8 TB/s HBM peak
-  cpu_baseline  the reference Fortran dycore (oracle/_ref, compiled from /root/reference)
+  cpu_baseline  the reference Fortran dycore (oracle/_ref, built by oracle/Makefile)
                 on the host cores, bounded sample
+  configs1      the same measurement on the x1.10242 mesh (BASELINE.json configs[1])
+  ranks, verify several blocks: one more step with HIP events around every exchange, and the owned
+                state against the whole mesh stepped as one block (bit for bit)
 """
 from __future__ import annotations
 
@@ -31,6 +38,8 @@ sys.path.insert(0, ROOT)
 
 METRIC = "dycore cell-updates/sec (nCells×nVertLevels/step) at 1/2/4/8 MI355X; % HBM roofline"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table (spec); 6.29 TB/s measured copy
+DUMP_FIELD_BYTES = 8 << 20  # --dump-outputs: per field; five fields stay well under 64 MB
+DUMP_SEED = 20260101
 
 
 def _dist():
@@ -145,6 +154,19 @@ def _cpu_model():
     return None
 
 
+def dump_sample(a, max_bytes: int = DUMP_FIELD_BYTES):
+    """A field as --dump-outputs stores it: float64, one row per column (cell or edge); of a field
+    larger than max_bytes, the rows of a sample of its columns in ascending order, drawn with a
+    fixed seed -- the same columns for every field of that shape, in every run and build."""
+    import numpy as np
+    a = np.asarray(a, dtype=np.float64)
+    a = a.reshape(a.shape[0], -1)
+    keep = max(1, max_bytes // (8 * a.shape[1]))
+    if a.shape[0] > keep:
+        a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep, replace=False))]
+    return np.ascontiguousarray(a)
+
+
 def small_mesh_line(args, torch, device, ncells=10242, steps=20, warmup=3):
     from mpas_dycore import Dycore
     from mpas_dycore.cases import jw_case
@@ -186,6 +208,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else this benchmark measures and checks: the "
+                         "acoustic roofline, the CPU baseline, the x1.10242 line (configs1) and, with several "
+                         "blocks, the exchange profile step and the verification against one block")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the prognostic state after the last timed step (u, theta_m, rho_zz, w, scalars at "
+                         "time level 1) as DIR/<field>.npy, float64; a field larger than 8 MB is stored as a "
+                         "fixed, seeded sample of its columns")
     ap.add_argument("--ncells", type=int, default=163842)
     ap.add_argument("--levels", type=int, default=56)
     ap.add_argument("--num-scalars", type=int, default=None)
@@ -393,10 +423,30 @@ def main():
     else:
         warm_up()
 
+    def dump_outputs():
+        """--dump-outputs: the state the last timed step left (time level 1 after its shift), the whole
+        mesh in global order on rank 0, as float64 .npy files of at most 8 MB each: a larger field is
+        a sample of its columns (cells or edges), drawn with a fixed seed from the field's shape."""
+        import numpy as np
+        from mpas_dycore import verify as V
+        wd.phase("dump outputs", args.phase_timeout)
+        if nparts > 1:
+            mine = V.owned_columns(blocks, lambda pool, name, ib: dy.get(pool, name, 1, block=ib))
+            parts = V.gather_to_root(dist, world, mine) if dist else [mine]
+            fields = V.assemble(parts, case) if rank == 0 else {}
+        else:
+            fields = {name: dy.get(pool, name, 1) for pool, name, _ in V.FIELDS}
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in fields.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), dump_sample(a))
+        wd.done()
+
     def timed_and_profile():
-        """The timed loop (barrier + synchronize on both sides) and, with several blocks, one more
-        step, eager, with HIP events around every exchange's exposed part (outside the timed region):
-        where this rank's time goes.  Returns (elapsed, graph replayed, per-rank profiles)."""
+        """The timed loop (barrier + synchronize on both sides), the --dump-outputs files and, with
+        --full and several blocks, one more step, eager, with HIP events around every exchange's
+        exposed part (outside the timed region): where this rank's time goes.  Returns (elapsed,
+        graph replayed, per-rank profiles)."""
         torch.cuda.synchronize(device)
         if dist:
             dist.barrier()
@@ -411,8 +461,10 @@ def main():
         t1 = time.perf_counter()
         wd.done()
         graph = dy.graph_active()
+        if args.dump_outputs:
+            dump_outputs()
         ranks = None
-        if nparts > 1:
+        if nparts > 1 and args.full:
             wd.phase("exchange profile step", args.phase_timeout)
             prof = dict(dy.exchange_profile(dt, args.warmup + args.steps + 1), rank=rank, owned_cells=int(owned),
                         halo_cells=int(halo))
@@ -473,7 +525,7 @@ def main():
         return ("one-sided" + (", send / receive buffers" if os.environ.get("MPAS_DYCORE_P2P_PULL") == "0" else "")
                 + (", no release fence" if os.environ.get("MPAS_DYCORE_P2P_RELEASE") == "0" else ""))
 
-    if nparts > 1 and not args.no_verify:
+    if nparts > 1 and args.full and not args.no_verify:
         verify = verify_run()
         verify["transport"] = transport_name()
         # after a mismatch over the one-sided transfer: RCCL groups; on one GPU (no RCCL between two
@@ -522,23 +574,33 @@ def main():
     # strong scaling: the whole x1.N mesh is advanced once per step, whatever the rank count
     value = case["nCells"] * case["nVertLevels"] / (ms_per_step / 1e3)
 
-    # ---- roofline of the acoustic sub-step (graded kernel), measured with HIP events
     nss = case["config"]["config_number_of_sub_steps"]
-    dts = dt / case["config"]["config_dynamics_split_steps"] / nss
-    ms_sub, ms_k = dy.time_acoustic_step(dts, small_step=2, reps=args.acoustic_reps)
-    b_ac = dy.acoustic_bytes()
-    t_kern = sum(ms_k) / 1e3
-    achieved = b_ac / t_kern / 1e9
-    traffic = None
-    tf = os.path.join(ROOT, "profiles", "acoustic_traffic.json")
-    if os.path.isfile(tf) and nparts == 1:  # the PMC figures are for the whole mesh as one block
-        try:
-            with open(tf) as f:
-                tj = json.load(f)
-            if tj.get("ncells") == case["nCells"] and tj.get("levels") == case["nVertLevels"]:
-                traffic = tj.get("bytes_per_substep")
-        except Exception:
-            traffic = None
+
+    def roofline():
+        """--full: roofline of the acoustic sub-step (graded kernel), measured with HIP events."""
+        dts = dt / case["config"]["config_dynamics_split_steps"] / nss
+        ms_sub, ms_k = dy.time_acoustic_step(dts, small_step=2, reps=args.acoustic_reps)
+        b_ac = dy.acoustic_bytes()
+        t_kern = sum(ms_k) / 1e3
+        achieved = b_ac / t_kern / 1e9
+        traffic = None
+        tf = os.path.join(ROOT, "profiles", "acoustic_traffic.json")
+        if os.path.isfile(tf) and nparts == 1:  # the PMC figures are for the whole mesh as one block
+            try:
+                with open(tf) as f:
+                    tj = json.load(f)
+                if tj.get("ncells") == case["nCells"] and tj.get("levels") == case["nVertLevels"]:
+                    traffic = tj.get("bytes_per_substep")
+            except Exception:
+                traffic = None
+        return {
+            "kernel": "acoustic sub-step (k_acoustic_edges<damped> + k_acoustic_cells; per sub-step of an "
+                      "--acoustic-reps loop as srk3 runs it, plus that loop's final k_divdamp)",
+            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "bytes_per_launch": b_ac, "ms_per_substep": sum(ms_k),
+            "ms_kernels": {"edges": ms_k[0], "cells": ms_k[1], "final_divdamp_share": ms_k[2]},
+        }
 
     out = {
         "metric": METRIC,
@@ -579,16 +641,12 @@ def main():
             "maxEdges_declared": [case["maxEdges"], case["maxEdges2"]],
             "kernel_layout": layout,
         },
-        "roofline": {
-            "kernel": "acoustic sub-step (k_acoustic_edges<damped> + k_acoustic_cells; per sub-step of an "
-                      "--acoustic-reps loop as srk3 runs it, plus that loop's final k_divdamp)",
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-            "bytes_per_launch": b_ac, "ms_per_substep": sum(ms_k),
-            "ms_kernels": {"edges": ms_k[0], "cells": ms_k[1], "final_divdamp_share": ms_k[2]},
-        },
+        "full": args.full,
+        "roofline": roofline() if args.full else None,
         "cpu_baseline": None,
     }
+    if args.dump_outputs:
+        out["dump_outputs"] = args.dump_outputs
     if nparts > 1:
         out["ranks"] = ranks
         out["preflight"] = preflight
@@ -596,7 +654,7 @@ def main():
         out["verify"] = verify
         if args.skip_pull:
             out["config"]["debug_skip_pull"] = args.skip_pull
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             # the box's CPU share for one GPU (OMP_NUM_THREADS there), not the machine's nproc
             nthreads = min(args.cpu_threads or int(os.environ.get("OMP_NUM_THREADS", "16")), os.cpu_count() or 1)
@@ -607,7 +665,7 @@ def main():
     dy.close()
     # BASELINE.json configs[1] (x1.10242 x 56 on one MI355X) alongside the headline mesh: the same
     # measurement on the small mesh (launch-bound), reported under "configs1"
-    if world == 1 and not (args.init or args.varres or args.no_configs1) and args.ncells != 10242:
+    if args.full and world == 1 and not (args.init or args.varres or args.no_configs1) and args.ncells != 10242:
         out["configs1"] = small_mesh_line(args, torch, device)
     if dist:
         dist.destroy_process_group()

@@ -3,7 +3,9 @@
 x1.N quasi-uniform icosahedral meshes with the JW baroclinic-wave state; dt and
 config_len_disp scale with resolution as SURVEY.md §8d lists them:
 2562 -> 2880 s / 480 km, 10242 -> 1440 s / 240 km, 163842 -> 360 s / 60 km.
-Cases are cached as .npz files (they take tens of seconds to build at 163842).
+Cases are cached as pickle files (they take tens of seconds to build at 163842) under
+$MPAS_DYCORE_CACHE, by default the user's cache directory ($XDG_CACHE_HOME or ~/.cache, mpas_dycore):
+what the build puts there (the benchmark's case) is still there when the benchmark runs.
 """
 from __future__ import annotations
 
@@ -16,7 +18,8 @@ import numpy as np
 from .init_atm import build_case
 from .mesh import build_mesh, build_varres_mesh
 
-CACHE = os.environ.get("MPAS_DYCORE_CACHE", "/tmp/mpas_dycore_cache")
+CACHE = os.environ.get("MPAS_DYCORE_CACHE") or os.path.join(
+    os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), "mpas_dycore")
 
 LEVEL_OF = {162: 2, 642: 3, 2562: 4, 10242: 5, 40962: 6, 163842: 7, 655362: 8}
 

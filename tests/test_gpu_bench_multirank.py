@@ -1,8 +1,8 @@
 """GPU: bench.py's multi-rank path as the driver runs it (torch.distributed.run, one process per rank,
 gloo rendezvous, host-side plan preflight, watchdog, max-over-ranks timing, per-rank exchange profile)
 with two ranks on the one GPU of the box (--same-device: no RCCL, the one-sided transfer between the
-two processes over IPC).  Checks the JSON contract of the line, not the speed, and the line's own
-verification: the ranks' owned state after the run equals the whole mesh stepped as one block on
+two processes over IPC), with --full for the profile and the check.  Checks the JSON contract of
+the line, not the speed, and the line's own verification: the ranks' owned state after the run equals the whole mesh stepped as one block on
 rank 0's GPU, bit for bit -- and with one exchange point's pull switched off (--skip-pull) the check
 fails, and the repeated run over the other transport passes."""
 import json
@@ -20,8 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _bench(port, *extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--ncells",
-           "10242", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-configs1", "--acoustic-reps", "3",
-           *extra]
+           "10242", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-configs1",
+           "--acoustic-reps", "3", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-3000:] + r.stderr[-3000:]

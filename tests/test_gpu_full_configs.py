@@ -19,7 +19,7 @@ box as a binary) run on the GPU box's host cores, 16 OpenMP threads.
     different sizes per block) bitwise equal to one block.
 
 Cases are built on the box (about a minute at 163842, a few at 835586) and cached under
-$MPAS_DYCORE_CACHE (default /tmp/mpas_dycore_cache), where bench.py finds them too.
+$MPAS_DYCORE_CACHE (default ~/.cache/mpas_dycore), where bench.py finds them too.
 Progress lines go to the real stderr so a long run shows it is alive.
 """
 import numpy as np

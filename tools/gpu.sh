@@ -6,8 +6,9 @@
 # limit).  Output goes to gpurun_out/<step>.log; a summary line per step goes to stdout.
 #   tests            pytest -m "gpu and not slow"            (TESTS="files or -k expr" to narrow)
 #   tests_full       pytest -m gpu (full-size BASELINE configs included)
-#   bench            bench.py default line (configs[2] mesh, configs[1] line, cpu_baseline)
-#   bench_fast       bench.py without cpu_baseline / configs[1] (BENCH_ARGS extra arguments)
+#   bench            bench.py plain line (configs[2] mesh: the timed steps only)
+#   bench_full       bench.py --full line on stdout (adds the roofline, the configs[1] line, cpu_baseline)
+#   bench_fast       bench.py --full without cpu_baseline / configs[1] (BENCH_ARGS extra arguments)
 #   bench55          bench_fast at 55 levels (the reference's default nVertLevels)
 #   moist            bench.py --moist (configs[3])
 #   varres           bench.py --varres 835586 (configs[4])
@@ -38,13 +39,15 @@
 #   floor            tools/gather_floor: the gather kernels next to load-only replays of their index streams
 #   smoke            __graft_entry__.smoke()
 cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out || exit 1
-B="--no-cpu-baseline --no-configs1"
+# bench.py --full without its two longest legs: the roofline, the exchange profile and the verification stay
+B="--full --no-cpu-baseline --no-configs1"
 last() { tail -1 "$1" | cut -c1-${2:-400}; }
 step() {
   case "$1" in
     tests) timeout -k 10 1000 python -u -m pytest -x -v --timeout 600 --timeout-method thread -m "gpu and not slow" ${TESTS:-tests} > gpurun_out/tests.log 2>&1; r=$?; tail -2 gpurun_out/tests.log; return $r ;;
     tests_full) timeout -k 10 1100 python -u -m pytest -x -v --durations=30 --timeout 900 --timeout-method thread -m gpu ${TESTS:-tests} > gpurun_out/tests_full.log 2>&1; r=$?; tail -2 gpurun_out/tests_full.log; return $r ;;
     bench) timeout -k 10 400 python bench.py --steps 10 --warmup 2 > gpurun_out/bench.log 2>&1 && last gpurun_out/bench.log 700 ;;
+    bench_full) timeout -k 10 600 python bench.py --full --steps 10 --warmup 2 | tail -1 | cut -c1-700 ;;
     bench_fast) timeout -k 10 300 python bench.py --steps 10 --warmup 2 $B ${BENCH_ARGS} > gpurun_out/bench_fast.log 2>&1 && last gpurun_out/bench_fast.log ;;
     bench55) timeout -k 10 300 python bench.py --steps 10 --warmup 2 $B --levels 55 > gpurun_out/bench55.log 2>&1 && last gpurun_out/bench55.log ;;
     moist) timeout -k 10 400 python bench.py --steps 10 --warmup 2 --moist $B > gpurun_out/moist.log 2>&1 && last gpurun_out/moist.log 300 ;;

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 B=${BENCH:-bench.py}
 for i in $(seq 1 ${N:-8}); do
   timeout -k 10 150 python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29600 + i)) \
-    $B --gpus 2 --same-device --ncells 10242 --steps 3 --warmup 1 --no-cpu-baseline --no-configs1 \
+    $B --gpus 2 --same-device --ncells 10242 --steps 3 --warmup 1 --full --no-cpu-baseline --no-configs1 \
     --acoustic-reps 3 --skip-pull tend.u. > gpurun_out/skip_$i.log 2>&1
   r=$?
   python -c "
