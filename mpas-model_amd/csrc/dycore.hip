@@ -25,6 +25,7 @@
 #include "api_rename.h"
 #endif
 #include "../../include/mpas_dycore.h"
+#include "p2p_wire.h"
 #include "kernels.hip"
 #include "halo.hip"
 #include "summary.hip"
@@ -106,6 +107,10 @@ struct XMsg {
 // this process directly (owned columns of one block -> halo columns of another); `post`
 // unpacks received RCCL messages.  One kernel launch each, whatever the number of blocks.
 struct XPlan {
+  // What a plan owns, released by free_plan: `owned`, every device allocation made for it
+  // (plan_alloc / plan_upload), and `mapped`, the peers' send buffers mapped here (IPC, a one-sided
+  // buffer plan).  Every device pointer below is a view into `owned`.
+  std::vector<void*> owned, mapped;
   XSeg* d_pre = nullptr;
   XSeg* d_post = nullptr;
   int npre = 0, npost = 0, maxn_pre = 0, maxn_post = 0;
@@ -121,7 +126,6 @@ struct XPlan {
   // phase or the stage's last damping) reads the receive buffer through `unpack`
   bool fused_unpack = false;
   std::vector<UnpackMap> unpack;    // per block
-  std::vector<void*> pack_mem;      // device allocations behind `pack`
   // the 876-887 and 642 exchanges fused into their producers and consumers (XPack / XUnpack,
   // dycore.h): then
   // fused_pack and fused_unpack are set too and these hold the per-block maps
@@ -139,7 +143,6 @@ struct XPlan {
   int nready = 0;
   const unsigned long long** d_cons = nullptr;  // the consumed flags this rank waits for
   int ncons = 0;
-  std::vector<void*> p2p_mapped;  // the peers' send buffers mapped here (IPC)
   // pull (k_p2p_pull): block-pair lists, blocking exchanges -- the receiver copies the peers' owned
   // columns from their fields; no buffers, no pack / unpack kernels, no fused pack / unpack
   bool pull = false;
@@ -150,9 +153,8 @@ struct XPlan {
   int nlocal = 0, maxn_local = 0;
   P2PSeg* d_pseg = nullptr;
   int2* d_chunk = nullptr;                // (segment, first column) per workgroup of k_p2p_pull
-  int npseg = 0, nchunk = 0, npeer_work = 0;
+  int nchunk = 0, npeer_work = 0;
   P2PPeer* d_peer = nullptr;
-  std::vector<void*> pull_mem;            // device copies of the peers' send lists
   // MPAS_DYCORE_P2P_SKIP (debugging, bench.py --skip-pull): the pull keeps its protocol but copies
   // each halo column onto itself, so the halo keeps its stale values -- a check that a wrong
   // exchange is seen (bench.py's one-block verification) can be seen to fail
@@ -198,13 +200,17 @@ struct mpas_dyc_ctx {
   // MPAS_DYCORE_P2P=1: messages between ranks of one node are pulled over xGMI by the receiving
   // rank's kernel (halo.hip k_p2p_get) instead of RCCL groups; RCCL stays for the set-up all-gathers
   int p2p = 0;
+  // one-sided transfer: owned for the context's life -- made by p2p_init and the pull set-up,
+  // released by p2p_teardown and nowhere else (p2p_setup.hip)
   unsigned long long* p2p_flags = nullptr;          // this rank's flag arena (uncached): [id][rank][2]
-  std::vector<unsigned long long*> p2p_peer_flags;  // by rank: the arenas of the peers, mapped here
-  std::vector<void*> p2p_mapped;                    // IPC mappings of the peers' arenas
-  int p2p_nr = 0;                                   // rank stride of the arena
-  int p2p_next = 0;                                 // the next exchange point's id
   int* p2p_status = nullptr;                        // set by a wait that timed out (halo.hip)
   int* p2p_status_host = nullptr;                   // pinned copy, read back after every step
+  // by rank: the peers' arenas mapped here (IPC); [rank] is p2p_flags itself
+  std::vector<unsigned long long*> p2p_peer_flags;
+  std::map<std::pair<int, uint64_t>, void*> p2p_fields;  // (rank, its field buffer) -> mapped here (IPC)
+  // one-sided transfer: state and switches
+  int p2p_nr = 0;                                   // rank stride of the arena
+  int p2p_next = 0;                                 // the next exchange point's id
   std::vector<XField> p2p_open;                     // a split-phase p2p exchange between post and get
   bool p2p_pending = false;
   bool p2p_merge = true;                            // MPAS_DYCORE_P2P_MERGE=0: post and get as two launches
@@ -216,7 +222,6 @@ struct mpas_dyc_ctx {
   // exchange on halo layer 1 only (the reference's own "SMALLER STENCIL?" note at 872); 2 = pv_edge /
   // rho_edge of the 1234-1249 exchange on edge layers 1-2 only.  MPAS_DYCORE_HALO_TRIM=0: all layers
   int halo_trim = 3;
-  std::map<std::pair<int, uint64_t>, void*> p2p_fields;  // (rank, its field buffer) -> mapped here
   // MPAS_DYCORE_LATE_ISSUE=1: a split-phase exchange is enqueued on the exchange stream at its
   // exchange_wait, after the compute kernels it overlaps (the same dependencies; only the order in
   // which a captured graph's nodes are created changes)
@@ -630,16 +635,47 @@ const XList* find_list(const Block& b, int loc, int layer, int dir, int peer_ran
   return nullptr;
 }
 
+// true if `key` contains one of the comma-separated substrings of `list` (a debugging switch's value)
+bool key_in_list(const char* list, const std::string& key) {
+  const std::string s = list ? list : "";
+  for (size_t a = 0; a < s.size();) {
+    size_t b = s.find(',', a);
+    if (b == std::string::npos) b = s.size();
+    if (b > a && key.find(s.substr(a, b - a)) != std::string::npos) return true;
+    a = b + 1;
+  }
+  return false;
+}
+
+// The one way a plan gets device memory: the allocation (at least 8 bytes) is recorded in pl.owned
+// the moment it exists, so free_plan frees it whatever fails later; `d` is a view.
+template <class T>
+int plan_alloc(mpas_dyc_ctx* ctx, XPlan& pl, T*& d, size_t bytes) {
+  void* p = nullptr;
+  HIPCHK(hipMalloc(&p, std::max<size_t>(bytes, 8)));
+  pl.owned.push_back(p);
+  d = (T*)p;
+  return MPAS_DYC_OK;
+}
+template <class T>
+int plan_upload(mpas_dyc_ctx* ctx, XPlan& pl, T*& d, const void* host, size_t bytes) {
+  CHK(plan_alloc(ctx, pl, d, bytes));
+  if (bytes) HIPCHK(hipMemcpy((void*)d, host, bytes, hipMemcpyHostToDevice));
+  return MPAS_DYC_OK;
+}
+
 void free_plan(XPlan& pl) {
-  for (void* p : pl.p2p_mapped) (void)hipIpcCloseMemHandle(p);
-  for (void* p : {(void*)pl.d_pre, (void*)pl.d_post, (void*)pl.sendbuf, (void*)pl.recvbuf, (void*)pl.p2p_cnt,
-                  (void*)pl.d_get, (void*)pl.d_ready, (void*)pl.d_cons})
-    if (p) (void)hipFree(p);
-  for (void* p : pl.pack_mem) (void)hipFree(p);
-  for (void* p : pl.pull_mem) (void)hipFree(p);
-  for (void* p : {(void*)pl.d_local, (void*)pl.d_pseg, (void*)pl.d_peer, (void*)pl.d_chunk})
-    if (p) (void)hipFree(p);
+  for (void* p : pl.mapped) (void)hipIpcCloseMemHandle(p);
+  for (void* p : pl.owned) (void)hipFree(p);
   pl = XPlan{};
+}
+
+// loopback: per emulated peer rank, its (send, receive) messages (either may be missing)
+std::map<int, std::pair<const XMsg*, const XMsg*>> loopback_pairs(const XPlan& pl) {
+  std::map<int, std::pair<const XMsg*, const XMsg*>> peers;
+  for (const XMsg& m : pl.rsend) peers[m.peer_rank].first = &m;
+  for (const XMsg& m : pl.rrecv) peers[m.peer_rank].second = &m;
+  return peers;
 }
 
 // captured steps bake pointers, list lengths and flags in: drop them when any of those changes
@@ -947,17 +983,8 @@ int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
   // set-up numbers the exchange points in the same order on every rank (flag indices, records)
   pl.p2p = ctx->p2p && (!pl.rsend.empty() || !pl.rrecv.empty() || ctx->nranks > 1);
   pl.pull = pl.p2p && ctx->p2p_pull && !positional && !split_phase(ctx);
-  if (pl.pull)
-    if (const char* bk = getenv("MPAS_DYCORE_P2P_BUFFERS")) {  // debugging: these exchange points (key substrings) in buffers mode
-      const std::string key = plan_key(ctx, fs), list = bk;
-      size_t a = 0;
-      while (a <= list.size()) {
-        size_t e = list.find(',', a);
-        if (e == std::string::npos) e = list.size();
-        if (e > a && key.find(list.substr(a, e - a)) != std::string::npos) pl.pull = false;
-        a = e + 1;
-      }
-    }
+  // debugging: MPAS_DYCORE_P2P_BUFFERS names exchange points (key substrings) to run in buffers mode
+  if (pl.pull && key_in_list(getenv("MPAS_DYCORE_P2P_BUFFERS"), plan_key(ctx, fs))) pl.pull = false;
   if (pl.pull) {
     // the receiver copies from the fields: no buffers, and the kernels store and read the fields
     // themselves (no fused pack / unpack)
@@ -974,10 +1001,7 @@ int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
         pl.maxn_local = std::max(pl.maxn_local, pre[i].n);
       }
     pl.nlocal = (int)loc.size();
-    if (pl.nlocal) {
-      HIPCHK(hipMalloc(&pl.d_local, loc.size() * sizeof(XSeg)));
-      HIPCHK(hipMemcpy(pl.d_local, loc.data(), loc.size() * sizeof(XSeg), hipMemcpyHostToDevice));
-    }
+    if (pl.nlocal) CHK(plan_upload(ctx, pl, pl.d_local, loc.data(), loc.size() * sizeof(XSeg)));
     return MPAS_DYC_OK;
   }
   if (pl.p2p) {
@@ -985,13 +1009,13 @@ int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
     // stores reach memory when its kernel ends (the L2 write-back that makes them visible to the
     // other XCDs), and the peers load it with system-scope loads (an uncached allocation here was
     // read stale by a peer process now and then: halo.hip)
-    HIPCHK(hipMalloc(&pl.sendbuf, std::max<int64_t>(stotal, 1) * sizeof(double) + 256));
+    CHK(plan_alloc(ctx, pl, pl.sendbuf, std::max<int64_t>(stotal, 1) * sizeof(double) + 256));
   } else if (stotal) {
-    HIPCHK(hipMalloc(&pl.sendbuf, stotal * sizeof(double)));
+    CHK(plan_alloc(ctx, pl, pl.sendbuf, stotal * sizeof(double)));
   }
   // 256 B of slack: a fused unpack (ld_pp) reads the two levels of its lane's pair, one past the
   // last column at an odd K
-  if (rtotal) HIPCHK(hipMalloc(&pl.recvbuf, rtotal * sizeof(double) + 256));
+  if (rtotal) CHK(plan_alloc(ctx, pl, pl.recvbuf, rtotal * sizeof(double) + 256));
   for (size_t i = 0; i < pre.size(); ++i)
     if (pre_off[i] >= 0) pre[i].dst = pl.sendbuf + pre_off[i];
   for (size_t i = 0; i < post.size(); ++i) post[i].src = pl.recvbuf + post_off[i];
@@ -1029,21 +1053,10 @@ int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
       }
       start[d.nCellsSolve] = (int)rt.size();
       if (rt.empty()) continue;
-      int* d_start = nullptr;
-      double** d_rt = nullptr;
-      double** d_rho = nullptr;
-      HIPCHK(hipMalloc(&d_start, start.size() * sizeof(int)));
-      HIPCHK(hipMemcpy(d_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
-      HIPCHK(hipMalloc(&d_rt, rt.size() * sizeof(double*)));
-      HIPCHK(hipMemcpy(d_rt, rt.data(), rt.size() * sizeof(double*), hipMemcpyHostToDevice));
-      pl.pack_mem.push_back(d_start);
-      pl.pack_mem.push_back(d_rt);
-      if (with_rho) {
-        HIPCHK(hipMalloc(&d_rho, rho.size() * sizeof(double*)));
-        HIPCHK(hipMemcpy(d_rho, rho.data(), rho.size() * sizeof(double*), hipMemcpyHostToDevice));
-        pl.pack_mem.push_back(d_rho);
-      }
-      pl.pack[bi] = PackMap{d_start, d_rt, d_rho};
+      PackMap& pm = pl.pack[bi];
+      CHK(plan_upload(ctx, pl, pm.start, start.data(), start.size() * sizeof(int)));
+      CHK(plan_upload(ctx, pl, pm.rt, rt.data(), rt.size() * sizeof(double*)));
+      if (with_rho) CHK(plan_upload(ctx, pl, pm.rho, rho.data(), rho.size() * sizeof(double*)));
     }
     pl.fused_pack = ctx->fused_pack_enabled;
     // unpack maps: halo cell -> its columns in the receive buffer (consumers: pair kernels only)
@@ -1065,16 +1078,10 @@ int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
           }
         }
         if (!any) continue;
-        int *d_rt = nullptr, *d_rho = nullptr;
-        HIPCHK(hipMalloc(&d_rt, std::max(nh, 1) * sizeof(int)));
-        HIPCHK(hipMemcpy(d_rt, rt.data(), nh * sizeof(int), hipMemcpyHostToDevice));
-        pl.pack_mem.push_back(d_rt);
-        if (with_rho) {
-          HIPCHK(hipMalloc(&d_rho, std::max(nh, 1) * sizeof(int)));
-          HIPCHK(hipMemcpy(d_rho, rho.data(), nh * sizeof(int), hipMemcpyHostToDevice));
-          pl.pack_mem.push_back(d_rho);
-        }
-        pl.unpack[bi] = UnpackMap{pl.recvbuf, d_rt, d_rho};
+        UnpackMap& um = pl.unpack[bi];
+        um.recv = pl.recvbuf;
+        CHK(plan_upload(ctx, pl, um.rt, rt.data(), nh * sizeof(int)));
+        if (with_rho) CHK(plan_upload(ctx, pl, um.rho, rho.data(), nh * sizeof(int)));
       }
       pl.fused_unpack = true;
     }
@@ -1083,12 +1090,6 @@ int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
     bool pair_all = true;
     for (int bi = 0; bi < nb; ++bi) pair_all = pair_all && pair_layout(ctx->blk[bi].d);
     if (pair_all) {
-      auto upload = [&](const void* h, size_t bytes, void** dptr) -> int {
-        HIPCHK(hipMalloc(dptr, std::max<size_t>(bytes, 4)));
-        if (bytes) HIPCHK(hipMemcpy(*dptr, h, bytes, hipMemcpyHostToDevice));
-        pl.pack_mem.push_back(*dptr);
-        return MPAS_DYC_OK;
-      };
       pl.rpk_cell.assign(nb, XPack{});
       pl.rpk_edge.assign(nb, XPack{});
       pl.rup_cell.assign(nb, XUnpack{});
@@ -1117,11 +1118,10 @@ int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
           }
           start[nsolve] = (int)fid.size();
           if (!fid.empty()) {
-            void *ds = nullptr, *df = nullptr, *dd = nullptr;
-            CHK(upload(start.data(), start.size() * sizeof(int), &ds));
-            CHK(upload(fid.data(), fid.size() * sizeof(int), &df));
-            CHK(upload(dst.data(), dst.size() * sizeof(double*), &dd));
-            (loc == L_CELL ? pl.rpk_cell : pl.rpk_edge)[bi] = XPack{(const int*)ds, (const int*)df, (double* const*)dd};
+            XPack& xp = (loc == L_CELL ? pl.rpk_cell : pl.rpk_edge)[bi];
+            CHK(plan_upload(ctx, pl, xp.start, start.data(), start.size() * sizeof(int)));
+            CHK(plan_upload(ctx, pl, xp.fid, fid.data(), fid.size() * sizeof(int)));
+            CHK(plan_upload(ctx, pl, xp.dst, dst.data(), dst.size() * sizeof(double*)));
           }
           // unpack: per field and halo element, its column in the receive buffer
           std::vector<int> off((size_t)nf * std::max(nh, 0), -1);
@@ -1156,14 +1156,12 @@ int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
               recfuse = false;
               break;
             }
-            void* dwb = nullptr;
-            CHK(upload(wb.data(), wb.size() * sizeof(int), &dwb));
-            d_wb = (const int*)dwb;
+            CHK(plan_upload(ctx, pl, d_wb, wb.data(), wb.size() * sizeof(int)));
           }
           if (any) {
-            void* doff = nullptr;
-            CHK(upload(off.data(), off.size() * sizeof(int), &doff));
-            (loc == L_CELL ? pl.rup_cell : pl.rup_edge)[bi] = XUnpack{pl.recvbuf, (const int*)doff, nh, d_wb};
+            const int* doff = nullptr;
+            CHK(plan_upload(ctx, pl, doff, off.data(), off.size() * sizeof(int)));
+            (loc == L_CELL ? pl.rup_cell : pl.rup_edge)[bi] = XUnpack{pl.recvbuf, doff, nh, d_wb};
           }
         }
       }
@@ -1178,14 +1176,8 @@ int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
       }
     }
   }
-  if (pl.npre) {
-    HIPCHK(hipMalloc(&pl.d_pre, pre.size() * sizeof(XSeg)));
-    HIPCHK(hipMemcpy(pl.d_pre, pre.data(), pre.size() * sizeof(XSeg), hipMemcpyHostToDevice));
-  }
-  if (pl.npost) {
-    HIPCHK(hipMalloc(&pl.d_post, post.size() * sizeof(XSeg)));
-    HIPCHK(hipMemcpy(pl.d_post, post.data(), post.size() * sizeof(XSeg), hipMemcpyHostToDevice));
-  }
+  if (pl.npre) CHK(plan_upload(ctx, pl, pl.d_pre, pre.data(), pre.size() * sizeof(XSeg)));
+  if (pl.npost) CHK(plan_upload(ctx, pl, pl.d_post, post.data(), post.size() * sizeof(XSeg)));
   return MPAS_DYC_OK;
 }
 
@@ -1213,10 +1205,7 @@ int rccl_group(mpas_dyc_ctx* ctx, const XPlan& pl) {
   if (ctx->loopback) {
     // one self pair per peer rank of max(send, receive) doubles (a peer this rank only sends to or
     // only receives from gets one too); build_plan sizes both buffers for it
-    std::map<int, std::pair<const XMsg*, const XMsg*>> peers;
-    for (const XMsg& m : pl.rsend) peers[m.peer_rank].first = &m;
-    for (const XMsg& m : pl.rrecv) peers[m.peer_rank].second = &m;
-    for (const auto& kv : peers) {
+    for (const auto& kv : loopback_pairs(pl)) {
       const XMsg *sm = kv.second.first, *rm = kv.second.second;
       const size_t n = (size_t)std::max(sm ? sm->count : 0, rm ? rm->count : 0);
       if (ctx->loopback == 2) {
@@ -1237,636 +1226,8 @@ int rccl_group(mpas_dyc_ctx* ctx, const XPlan& pl) {
   return MPAS_DYC_OK;
 }
 
-// ---------------------------------------------------------------------------
-// one-sided transfer set-up (MPAS_DYCORE_P2P, halo.hip): collective, outside graph capture
-// ---------------------------------------------------------------------------
-constexpr int P2P_MAX_POINTS = 4096;  // exchange points per context (a run builds ~60)
-
-// nbytes from every rank, in rank order, over the library's communicator
-int allgather_bytes(mpas_dyc_ctx* ctx, const void* mine, size_t nbytes, std::vector<char>& all) {
-  all.assign(nbytes * ctx->nranks, 0);
-  if (ctx->nranks == 1) {
-    memcpy(all.data(), mine, nbytes);
-    return MPAS_DYC_OK;
-  }
-  if (ctx->host_allgather) {  // the host's collective, even beside an RCCL communicator (kept for fallback)
-    if (ctx->host_allgather(mine, all.data(), (int64_t)nbytes, ctx->host_user) != 0) {
-      ctx->err = "the host's all-gather (mpas_dyc_comm_init_host) failed";
-      return MPAS_DYC_ECOMM;
-    }
-    return MPAS_DYC_OK;
-  }
-  char* d = nullptr;
-  HIPCHK(hipMalloc(&d, nbytes * (ctx->nranks + 1)));
-  const int r = [&]() -> int {
-    HIPCHK(hipMemcpy(d, mine, nbytes, hipMemcpyHostToDevice));
-    NCCLCHK(ncclAllGather(d, d + nbytes, nbytes, ncclUint8, ctx->comm, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpy(all.data(), d + nbytes, nbytes * ctx->nranks, hipMemcpyDeviceToHost));
-    return MPAS_DYC_OK;
-  }();
-  (void)hipFree(d);
-  return r;
-}
-
-// the node a rank runs on: IPC mappings exist only between processes of one node
-uint64_t node_id() {
-  char buf[512] = {0};
-  (void)gethostname(buf, 255);
-  if (FILE* f = fopen("/proc/sys/kernel/random/boot_id", "r")) {
-    const size_t n = strlen(buf);
-    if (!fgets(buf + n, (int)(sizeof(buf) - n - 1), f)) buf[n] = 0;
-    fclose(f);
-  }
-  uint64_t h = 1469598103934665603ull;
-  for (const char* c = buf; *c; ++c) h = (h ^ (unsigned char)*c) * 1099511628211ull;
-  return h;
-}
-
-// p2p_init / p2p_setup return this when the one-sided transfer cannot run on some rank (IPC
-// unsupported, ranks on several nodes, a mapping refused): every rank learns it from the same
-// all-gathers, drops the transfer and plans again with RCCL (plan_all, p2p_fallback)
-constexpr int P2P_UNAVAILABLE = 1;
-
-// every rank's verdict on a local step of the set-up (collective): P2P_UNAVAILABLE on all ranks if
-// any rank failed, with the first failing rank's reason in ctx->err
-int p2p_vote(mpas_dyc_ctx* ctx, int local, const std::string& what) {
-  int32_t mine = local == MPAS_DYC_OK ? 0 : 1;
-  std::vector<char> all;
-  CHK(allgather_bytes(ctx, &mine, sizeof(mine), all));
-  for (int r = 0; r < ctx->nranks; ++r)
-    if (((const int32_t*)all.data())[r]) {
-      ctx->err = "one-sided transfer unavailable (" + what + " failed on rank " + std::to_string(r) +
-                 (r == ctx->rank ? ": " + ctx->err : std::string()) + ")";
-      return P2P_UNAVAILABLE;
-    }
-  return MPAS_DYC_OK;
-}
-
-// the flag arenas: this rank's, and every peer's mapped here
-int p2p_init(mpas_dyc_ctx* ctx) {
-  if (ctx->p2p_flags) return MPAS_DYC_OK;
-  if (!ctx->comm && !ctx->host_allgather) {
-    ctx->err = "MPAS_DYCORE_P2P: no communicator for the set-up (mpas_dyc_comm_init / _comm_init_host)";
-    return MPAS_DYC_ECOMM;
-  }
-  int nr = ctx->nranks;
-  if (ctx->loopback)  // the emulated peers are ranks the lists name, beyond this one-rank communicator
-    for (const auto& b : ctx->blk)
-      for (const auto& x : b.xl) nr = std::max(nr, x.peer_rank + 1);
-  ctx->p2p_nr = nr;
-  struct Rec {
-    hipIpcMemHandle_t h;
-    uint64_t node;
-  } rec{};
-  const int local = [&]() -> int {
-    const size_t bytes = (size_t)P2P_MAX_POINTS * nr * 2 * sizeof(unsigned long long);
-    HIPCHK(hipExtMallocWithFlags((void**)&ctx->p2p_flags, bytes, hipDeviceMallocUncached));
-    HIPCHK(hipMemset(ctx->p2p_flags, 0, bytes));
-    HIPCHK(hipMalloc(&ctx->p2p_status, sizeof(int)));
-    HIPCHK(hipMemset(ctx->p2p_status, 0, sizeof(int)));
-    HIPCHK(hipHostMalloc((void**)&ctx->p2p_status_host, sizeof(int), hipHostMallocDefault));
-    *ctx->p2p_status_host = 0;
-    HIPCHK(hipDeviceSynchronize());
-    if (ctx->nranks > 1) HIPCHK(hipIpcGetMemHandle(&rec.h, ctx->p2p_flags));
-    return MPAS_DYC_OK;
-  }();
-  ctx->p2p_peer_flags.assign(ctx->nranks, nullptr);
-  ctx->p2p_peer_flags[ctx->rank] = ctx->p2p_flags;
-  if (ctx->nranks == 1) return local;
-  CHK(p2p_vote(ctx, local, "flag arena allocation"));
-  rec.node = node_id();
-  std::vector<char> all;
-  CHK(allgather_bytes(ctx, &rec, sizeof(rec), all));
-  for (int r = 0; r < ctx->nranks; ++r)
-    if (((const Rec*)all.data())[r].node != rec.node) {
-      ctx->err = "one-sided transfer unavailable (rank " + std::to_string(r) + " runs on another node)";
-      return P2P_UNAVAILABLE;
-    }
-  const int opened = [&]() -> int {
-    for (int r = 0; r < ctx->nranks; ++r) {
-      if (r == ctx->rank) continue;
-      void* p = nullptr;
-      HIPCHK(hipIpcOpenMemHandle(&p, ((const Rec*)all.data())[r].h, hipIpcMemLazyEnablePeerAccess));
-      ctx->p2p_mapped.push_back(p);
-      ctx->p2p_peer_flags[r] = (unsigned long long*)p;
-    }
-    return MPAS_DYC_OK;
-  }();
-  return p2p_vote(ctx, opened, "mapping the peers' flag arenas");
-}
-
-// Maps the send buffers of the exchange points built since the last call and uploads their get /
-// post tables.  Every rank builds the same exchange points in the same (plan key) order; the count
-// is checked, and every message's size against its sender's.
-int p2p_setup_pull(mpas_dyc_ctx* ctx, const std::vector<XPlan*>& todo);
-
-// MPAS_DYCORE_P2P_SKIP=key[,key...]: the pull plans whose plan key contains one of the substrings
-bool p2p_skip_match(const std::string& key) {
-  const char* env = getenv("MPAS_DYCORE_P2P_SKIP");
-  if (!env || !*env) return false;
-  std::string s(env);
-  size_t a = 0;
-  while (a <= s.size()) {
-    size_t b = s.find(',', a);
-    if (b == std::string::npos) b = s.size();
-    if (b > a && key.find(s.substr(a, b - a)) != std::string::npos) return true;
-    a = b + 1;
-  }
-  return false;
-}
-
-int p2p_setup(mpas_dyc_ctx* ctx) {
-  std::vector<XPlan*> todo, pulls;
-  for (auto& kv : ctx->plans)
-    if (kv.second.p2p && kv.second.p2p_id < 0) {
-      kv.second.skip_pull = kv.second.pull && p2p_skip_match(kv.first);
-      (kv.second.pull ? pulls : todo).push_back(&kv.second);
-    }
-  // nothing to map and no peer process to agree with (a single block, or only in-process copies)
-  if (todo.empty() && pulls.empty() && ctx->nranks == 1) return MPAS_DYC_OK;
-  CHK(p2p_init(ctx));
-  const int nr = ctx->nranks, me = ctx->rank;
-  {
-    // every rank must set up the same exchange points, split the same way into pull and buffer plans,
-    // with the same next flag slot: pulls and buffers take different all-gathers below (a rank whose
-    // environment -- MPAS_DYCORE_P2P_PULL / _BUFFERS / _OVERLAP -- or lists differ would pair its
-    // all-gathers with other ones), and the slot numbers name the flags the peers wait on
-    const int64_t n[3] = {(int64_t)pulls.size(), (int64_t)todo.size(), (int64_t)ctx->p2p_next};
-    std::vector<char> all;
-    CHK(allgather_bytes(ctx, n, sizeof(n), all));
-    for (int r = 0; r < nr; ++r) {
-      const int64_t* o = (const int64_t*)all.data() + 3 * (size_t)r;
-      if (o[0] != n[0] || o[1] != n[1] || o[2] != n[2]) {
-        ctx->err = "MPAS_DYCORE_P2P: rank " + std::to_string(r) + " sets up " + std::to_string(o[0]) + " pull and " +
-                   std::to_string(o[1]) + " buffer exchange points from flag slot " + std::to_string(o[2]) +
-                   ", rank " + std::to_string(me) + " " + std::to_string(n[0]) + " and " + std::to_string(n[1]) +
-                   " from slot " + std::to_string(n[2]) + " (every rank must run the same exchange sequence with the "
-                   "same MPAS_DYCORE_P2P_* settings)";
-        return MPAS_DYC_ECOMM;
-      }
-    }
-  }
-  CHK(p2p_setup_pull(ctx, pulls));
-  if (todo.empty()) return MPAS_DYC_OK;
-  // per exchange point: the send buffer's IPC handle, then per rank (offset, count) of the message to it
-  const size_t per = sizeof(hipIpcMemHandle_t) + 2 * sizeof(int64_t) * nr;
-  std::vector<char> mine(per * todo.size(), 0), all;
-  const int handles = [&]() -> int {
-    for (size_t i = 0; i < todo.size(); ++i) {
-      char* r = mine.data() + per * i;
-      if (nr > 1) HIPCHK(hipIpcGetMemHandle((hipIpcMemHandle_t*)r, todo[i]->sendbuf));
-      int64_t* oc = (int64_t*)(r + sizeof(hipIpcMemHandle_t));
-      for (int q = 0; q < nr; ++q) oc[2 * q] = oc[2 * q + 1] = -1;
-      for (const XMsg& m : todo[i]->rsend) {
-        if (m.peer_rank >= nr) continue;  // loopback: emulated ranks beyond the communicator
-        oc[2 * m.peer_rank] = m.off;
-        oc[2 * m.peer_rank + 1] = m.count;
-      }
-    }
-    return MPAS_DYC_OK;
-  }();
-  if (nr > 1) CHK(p2p_vote(ctx, handles, "exporting the send buffers"));
-  else CHK(handles);
-  CHK(allgather_bytes(ctx, mine.data(), mine.size(), all));
-  const int built = [&]() -> int {
-    for (size_t i = 0; i < todo.size(); ++i) {
-      XPlan& pl = *todo[i];
-      if (ctx->p2p_next >= P2P_MAX_POINTS) {
-        ctx->err = "MPAS_DYCORE_P2P: more than " + std::to_string(P2P_MAX_POINTS) + " exchange points";
-        return MPAS_DYC_ESTATE;
-      }
-      pl.p2p_id = ctx->p2p_next++;
-      auto flag = [&](unsigned long long* arena, int r, int k) {
-        return arena + ((size_t)pl.p2p_id * ctx->p2p_nr + r) * 2 + k;
-      };
-      auto nchunk = [](int64_t n) { return (int)std::max<int64_t>(1, (n + P2P_CHUNK - 1) / P2P_CHUNK); };
-      std::vector<P2PGet> gets;
-      std::vector<unsigned long long*> ready;
-      std::vector<const unsigned long long*> cons;
-      if (ctx->loopback) {
-        // as rccl_group: one pair per emulated peer of max(send, receive) doubles, all in this rank
-        std::map<int, std::pair<const XMsg*, const XMsg*>> peers;
-        for (const XMsg& m : pl.rsend) peers[m.peer_rank].first = &m;
-        for (const XMsg& m : pl.rrecv) peers[m.peer_rank].second = &m;
-        for (const auto& kv : peers) {
-          const XMsg *sm = kv.second.first, *rm = kv.second.second;
-          const int64_t n = std::max(sm ? sm->count : 0, rm ? rm->count : 0);
-          gets.push_back(P2PGet{pl.sendbuf + (sm ? sm->off : 0), pl.recvbuf + (rm ? rm->off : 0), n,
-                                flag(ctx->p2p_flags, kv.first, 0), flag(ctx->p2p_flags, kv.first, 1), nullptr,
-                                nchunk(n)});
-          ready.push_back(flag(ctx->p2p_flags, kv.first, 0));
-          cons.push_back(flag(ctx->p2p_flags, kv.first, 1));
-        }
-      } else {
-        for (const XMsg& m : pl.rsend) {
-          ready.push_back(flag(ctx->p2p_peer_flags[m.peer_rank], me, 0));
-          cons.push_back(flag(ctx->p2p_flags, m.peer_rank, 1));
-        }
-        for (const XMsg& m : pl.rrecv) {
-          const char* rr = all.data() + (size_t)m.peer_rank * mine.size() + per * i;
-          const int64_t* oc = (const int64_t*)(rr + sizeof(hipIpcMemHandle_t));
-          if (oc[2 * me + 1] != m.count) {
-            ctx->err = "MPAS_DYCORE_P2P: rank " + std::to_string(m.peer_rank) + " sends " +
-                       std::to_string(oc[2 * me + 1]) + " doubles where this rank receives " + std::to_string(m.count);
-            return MPAS_DYC_ECOMM;
-          }
-          const double* base = pl.sendbuf;
-          if (m.peer_rank != me) {
-            void* p = nullptr;
-            HIPCHK(hipIpcOpenMemHandle(&p, *(const hipIpcMemHandle_t*)rr, hipIpcMemLazyEnablePeerAccess));
-            pl.p2p_mapped.push_back(p);
-            base = (const double*)p;
-          }
-          gets.push_back(P2PGet{base + oc[2 * me], pl.recvbuf + m.off, m.count, flag(ctx->p2p_flags, m.peer_rank, 0),
-                                flag(ctx->p2p_peer_flags[m.peer_rank], me, 1), nullptr, nchunk(m.count)});
-        }
-      }
-      if (cons.size() > 256 || ready.size() > 256) {
-        ctx->err = "MPAS_DYCORE_P2P: more than 256 peers";
-        return MPAS_DYC_EINVAL;
-      }
-      // [0] uses, [1 + i] chunks pulled from get peer i, [1 + nget] finished workgroups of k_p2p_exchange
-      HIPCHK(hipMalloc(&pl.p2p_cnt, (2 + gets.size()) * sizeof(unsigned long long)));
-      HIPCHK(hipMemset(pl.p2p_cnt, 0, (2 + gets.size()) * sizeof(unsigned long long)));
-      for (size_t j = 0; j < gets.size(); ++j) {
-        gets[j].done = pl.p2p_cnt + 1 + j;
-        pl.get_chunks = std::max(pl.get_chunks, gets[j].nchunk);
-      }
-      pl.nget = (int)gets.size();
-      pl.nready = (int)ready.size();
-      pl.ncons = (int)cons.size();
-      auto upload = [&](const void* h, size_t bytes, void** d) -> int {
-        HIPCHK(hipMalloc(d, std::max<size_t>(bytes, 8)));
-        if (bytes) HIPCHK(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-        return MPAS_DYC_OK;
-      };
-      CHK(upload(gets.data(), gets.size() * sizeof(P2PGet), (void**)&pl.d_get));
-      CHK(upload(ready.data(), ready.size() * sizeof(void*), (void**)&pl.d_ready));
-      CHK(upload(cons.data(), cons.size() * sizeof(void*), (void**)&pl.d_cons));
-    }
-    return MPAS_DYC_OK;
-  }();
-  return nr > 1 ? p2p_vote(ctx, built, "mapping the peers' send buffers") : built;
-}
-
-// variable-size all-gather: every rank's bytes, in rank order
-int allgatherv_bytes(mpas_dyc_ctx* ctx, const std::vector<char>& mine, std::vector<std::vector<char>>& out) {
-  int64_t n = (int64_t)mine.size();
-  std::vector<char> sizes;
-  CHK(allgather_bytes(ctx, &n, sizeof(n), sizes));
-  int64_t mx = 0;
-  for (int r = 0; r < ctx->nranks; ++r) mx = std::max(mx, ((const int64_t*)sizes.data())[r]);
-  std::vector<char> pad(mine);
-  pad.resize(std::max<int64_t>(mx, 1), 0);
-  std::vector<char> all;
-  CHK(allgather_bytes(ctx, pad.data(), pad.size(), all));
-  out.assign(ctx->nranks, {});
-  for (int r = 0; r < ctx->nranks; ++r) {
-    const char* b = all.data() + (size_t)r * pad.size();
-    out[r].assign(b, b + ((const int64_t*)sizes.data())[r]);
-  }
-  return MPAS_DYC_OK;
-}
-
-// Pull plans: every rank exports, per exchange point and message, its pack segments (the field
-// buffer -- IPC handle, mapped once per peer and buffer -- the sub-field offset, the send list);
-// the receiver pairs them in message order with its unpack segments into k_p2p_pull's segments.
-int p2p_setup_pull(mpas_dyc_ctx* ctx, const std::vector<XPlan*>& todo) {
-  const int nr = ctx->nranks, me = ctx->rank;
-  if (todo.empty()) return MPAS_DYC_OK;
-  // the field buffer a pack segment reads
-  auto base_of = [&](const double* p, size_t& bytes) -> const double* {
-    for (const auto& b : ctx->blk)
-      for (const auto& f : b.fields)
-        for (int t = 0; t < f.ntl; ++t) {
-          const char* q = (const char*)f.buf[t];
-          if (!q || f.is_int) continue;
-          const size_t nb = (size_t)field_bytes(b, f) + 256;
-          if ((const char*)p >= q && (const char*)p < q + nb) {
-            bytes = nb;
-            return (const double*)q;
-          }
-        }
-    return nullptr;
-  };
-  std::vector<char> rec;
-  auto put = [&](const void* v, size_t n) { rec.insert(rec.end(), (const char*)v, (const char*)v + n); };
-  std::vector<const double*> bases;
-  std::map<const double*, int32_t> base_id;
-  std::vector<char> body;
-  const int exported = [&]() -> int {
-    std::vector<char> hdr;
-    for (XPlan* pp : todo) {
-      const XPlan& pl = *pp;
-      const int32_t nmsg = (int32_t)pl.rsend.size();
-      body.insert(body.end(), (const char*)&nmsg, (const char*)&nmsg + 4);
-      for (const XMsg& m : pl.rsend) {
-        std::vector<size_t> segs;  // in buffer order: the receiver pairs them with its unpack segments so
-        for (size_t i = 0; i < pl.h_pre.size(); ++i)
-          if (pl.h_pre_off[i] >= m.off && pl.h_pre_off[i] < m.off + m.count) segs.push_back(i);
-        std::sort(segs.begin(), segs.end(), [&](size_t a, size_t b) { return pl.h_pre_off[a] < pl.h_pre_off[b]; });
-        const int32_t dest = m.peer_rank, ns = (int32_t)segs.size();
-        body.insert(body.end(), (const char*)&dest, (const char*)&dest + 4);
-        body.insert(body.end(), (const char*)&ns, (const char*)&ns + 4);
-        for (size_t i : segs) {
-          const XSeg& sg = pl.h_pre[i];
-          size_t nb = 0;
-          const double* b = base_of(sg.src, nb);
-          if (!b) {
-            ctx->err = "internal: pack segment outside every field";
-            return MPAS_DYC_ESTATE;
-          }
-          if (!base_id.count(b)) {
-            base_id[b] = (int32_t)bases.size();
-            bases.push_back(b);
-          }
-          const int32_t id = base_id[b], n = sg.n, inner = sg.inner;
-          const int64_t off = (const char*)sg.src - (const char*)b;
-          const std::vector<int32_t>& idx = *pl.h_pre_idx[i];
-          body.insert(body.end(), (const char*)&id, (const char*)&id + 4);
-          body.insert(body.end(), (const char*)&off, (const char*)&off + 8);
-          body.insert(body.end(), (const char*)&n, (const char*)&n + 4);
-          body.insert(body.end(), (const char*)&inner, (const char*)&inner + 4);
-          body.insert(body.end(), (const char*)idx.data(), (const char*)(idx.data() + n));
-        }
-      }
-    }
-    const int32_t nbase = (int32_t)bases.size();
-    put(&nbase, 4);
-    for (const double* b : bases) {
-      const uint64_t a = (uint64_t)(uintptr_t)b;
-      hipIpcMemHandle_t h{};
-      if (nr > 1) HIPCHK(hipIpcGetMemHandle(&h, (void*)b));
-      put(&a, 8);
-      put(&h, sizeof(h));
-    }
-    rec.insert(rec.end(), body.begin(), body.end());
-    return MPAS_DYC_OK;
-  }();
-  if (nr > 1) CHK(p2p_vote(ctx, exported, "exporting the field buffers"));
-  else CHK(exported);
-  std::vector<std::vector<char>> all;
-  CHK(allgatherv_bytes(ctx, rec, all));
-  // per rank: its buffer table and a cursor over its per-plan messages
-  // (every rank parses every rank's record, so a malformed one fails on all ranks alike)
-  struct Reader {
-    const char* p;
-    const char* end;
-    std::vector<std::pair<uint64_t, hipIpcMemHandle_t>> bases;
-    bool has(size_t n) const { return (size_t)(end - p) >= n; }
-  };
-  auto truncated = [&](int r) {
-    ctx->err = "MPAS_DYCORE_P2P: rank " + std::to_string(r) + "'s pull record ends early (its exchange points or "
-               "messages differ from rank " + std::to_string(me) + "'s)";
-    return MPAS_DYC_ECOMM;
-  };
-  std::vector<Reader> rd(nr);
-  for (int r = 0; r < nr; ++r) {
-    Reader& R = rd[r];
-    R.p = all[r].data();
-    R.end = R.p + all[r].size();
-    int32_t nb;
-    if (!R.has(4)) return truncated(r);
-    memcpy(&nb, R.p, 4);
-    R.p += 4;
-    if (nb < 0) return truncated(r);
-    for (int i = 0; i < nb; ++i) {
-      std::pair<uint64_t, hipIpcMemHandle_t> e;
-      if (!R.has(8 + sizeof(hipIpcMemHandle_t))) return truncated(r);
-      memcpy(&e.first, R.p, 8);
-      memcpy(&e.second, R.p + 8, sizeof(hipIpcMemHandle_t));
-      R.p += 8 + sizeof(hipIpcMemHandle_t);
-      R.bases.push_back(e);
-    }
-  }
-  struct SegIn {
-    int32_t id, n, inner;
-    int64_t off;
-    const int32_t* idx;
-  };
-  // a mapped field buffer of rank r (each buffer opened once per context)
-  auto mapped = [&](int r, int32_t id, const double*& out) -> int {
-    const auto& e = rd[r].bases.at(id);
-    if (r == me) {
-      out = (const double*)(uintptr_t)e.first;
-      return MPAS_DYC_OK;
-    }
-    auto key = std::make_pair(r, e.first);
-    auto it = ctx->p2p_fields.find(key);
-    if (it == ctx->p2p_fields.end()) {
-      void* p = nullptr;
-      HIPCHK(hipIpcOpenMemHandle(&p, e.second, hipIpcMemLazyEnablePeerAccess));
-      ctx->p2p_mapped.push_back(p);
-      it = ctx->p2p_fields.emplace(key, p).first;
-    }
-    out = (const double*)it->second;
-    return MPAS_DYC_OK;
-  };
-  const int built = [&]() -> int {
-    for (XPlan* pp : todo) {
-      XPlan& pl = *pp;
-      if (ctx->p2p_next >= P2P_MAX_POINTS) {
-        ctx->err = "MPAS_DYCORE_P2P: more than " + std::to_string(P2P_MAX_POINTS) + " exchange points";
-        return MPAS_DYC_ESTATE;
-      }
-      pl.p2p_id = ctx->p2p_next++;
-      auto flag = [&](unsigned long long* arena, int r, int k) {
-        return arena + ((size_t)pl.p2p_id * ctx->p2p_nr + r) * 2 + k;
-      };
-      // every rank's messages of this exchange point: rank -> destination -> its pack segments
-      std::vector<std::map<int, std::vector<SegIn>>> from(nr);
-      for (int r = 0; r < nr; ++r) {
-        Reader& R = rd[r];
-        const char*& q = R.p;
-        int32_t nmsg;
-        if (!R.has(4)) return truncated(r);
-        memcpy(&nmsg, q, 4);
-        q += 4;
-        if (nmsg < 0) return truncated(r);
-        for (int m = 0; m < nmsg; ++m) {
-          int32_t dest, ns;
-          if (!R.has(8)) return truncated(r);
-          memcpy(&dest, q, 4);
-          memcpy(&ns, q + 4, 4);
-          q += 8;
-          if (ns < 0) return truncated(r);
-          auto& v = from[r][dest];
-          for (int k = 0; k < ns; ++k) {
-            SegIn si{};
-            if (!R.has(20)) return truncated(r);
-            memcpy(&si.id, q, 4);
-            memcpy(&si.off, q + 4, 8);
-            memcpy(&si.n, q + 12, 4);
-            memcpy(&si.inner, q + 16, 4);
-            if (si.n < 0 || !R.has(20 + 4 * (size_t)si.n) || si.id < 0 || (size_t)si.id >= R.bases.size())
-              return truncated(r);
-            si.idx = (const int32_t*)(q + 20);
-            q += 20 + 4 * (size_t)si.n;
-            v.push_back(si);
-          }
-        }
-      }
-      std::vector<P2PSeg> segs;
-      std::vector<P2PPeer> peers;
-      std::vector<unsigned long long*> ready;
-      std::vector<const unsigned long long*> cons;
-      std::map<int, int> peer_ix;
-      auto peer_of = [&](int src) -> int {
-        auto it = peer_ix.find(src);
-        if (it != peer_ix.end()) return it->second;
-        const int ix = (int)peers.size();
-        peer_ix[src] = ix;
-        const bool here = ctx->loopback || src == me;
-        peers.push_back(P2PPeer{flag(ctx->p2p_flags, src, 0),
-                                here ? flag(ctx->p2p_flags, src, 1) : flag(ctx->p2p_peer_flags[src], me, 1), nullptr, 0});
-        return ix;
-      };
-      auto upload = [&](const void* h, size_t bytes) -> void* {
-        void* d = nullptr;
-        if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-        if (bytes && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-          (void)hipFree(d);
-          return nullptr;
-        }
-        pl.pull_mem.push_back(d);
-        return d;
-      };
-      std::set<int> loop_peers;  // loopback: every emulated peer
-      for (const XMsg& m : pl.rrecv) {
-        std::vector<size_t> mine_post;  // in buffer order, as the sender exported its pack segments
-        for (size_t i = 0; i < pl.h_post.size(); ++i)
-          if (pl.h_post_off[i] >= m.off && pl.h_post_off[i] < m.off + m.count) mine_post.push_back(i);
-        std::sort(mine_post.begin(), mine_post.end(),
-                  [&](size_t a, size_t b) { return pl.h_post_off[a] < pl.h_post_off[b]; });
-        const int src = m.peer_rank;
-        const int ix = peer_of(src);
-        if (ctx->loopback) {
-          // timing only: the peer's segments are this rank's own pack segments to that peer
-          loop_peers.insert(src);
-          std::vector<size_t> theirs;
-          for (const XMsg& sm : pl.rsend)
-            if (sm.peer_rank == src)
-              for (size_t i = 0; i < pl.h_pre.size(); ++i)
-                if (pl.h_pre_off[i] >= sm.off && pl.h_pre_off[i] < sm.off + sm.count) theirs.push_back(i);
-          std::sort(theirs.begin(), theirs.end(), [&](size_t a, size_t b) { return pl.h_pre_off[a] < pl.h_pre_off[b]; });
-          for (size_t k = 0; k < std::min(theirs.size(), mine_post.size()); ++k) {
-            const XSeg &a = pl.h_pre[theirs[k]], &b = pl.h_post[mine_post[k]];
-            const int n = std::min(a.n, b.n);
-            segs.push_back(P2PSeg{a.src, b.dst, a.sidx, b.didx, n, std::min(a.inner, b.inner), ix});
-          }
-          continue;
-        }
-        auto f = from[src].find(me);
-        if (f == from[src].end() || f->second.size() != mine_post.size()) {
-          ctx->err = "MPAS_DYCORE_P2P: rank " + std::to_string(src) + "'s message to rank " + std::to_string(me) +
-                     " does not match this rank's receive lists";
-          return MPAS_DYC_ECOMM;
-        }
-        for (size_t k = 0; k < mine_post.size(); ++k) {
-          const SegIn& a = f->second[k];
-          const XSeg& b = pl.h_post[mine_post[k]];
-          if (a.n != b.n || a.inner != b.inner) {
-            ctx->err = "MPAS_DYCORE_P2P: rank " + std::to_string(src) + " sends " + std::to_string(a.n) +
-                       " elements where rank " + std::to_string(me) + " receives " + std::to_string(b.n);
-            return MPAS_DYC_ECOMM;
-          }
-          if (pl.skip_pull) {  // each halo column onto itself: the protocol runs, the halo stays stale
-            segs.push_back(P2PSeg{b.dst, b.dst, b.didx, b.didx, a.n, a.inner, ix});
-            continue;
-          }
-          const double* base = nullptr;
-          CHK(mapped(src, a.id, base));
-          const int* sidx = (const int*)upload(a.idx, sizeof(int32_t) * (size_t)a.n);
-          if (!sidx) {
-            ctx->err = "hipMalloc for a peer's send list failed";
-            return MPAS_DYC_EHIP;
-          }
-          segs.push_back(P2PSeg{(const double*)((const char*)base + a.off), b.dst, sidx, b.didx, a.n, a.inner, ix});
-        }
-      }
-      if (ctx->loopback) {
-        for (const XMsg& m : pl.rsend) {
-          loop_peers.insert(m.peer_rank);
-          (void)peer_of(m.peer_rank);
-        }
-        for (int q : loop_peers) ready.push_back(flag(ctx->p2p_flags, q, 0));
-      } else {
-        for (const XMsg& m : pl.rsend) {
-          ready.push_back(flag(ctx->p2p_peer_flags[m.peer_rank], me, 0));
-          cons.push_back(flag(ctx->p2p_flags, m.peer_rank, 1));
-        }
-      }
-      std::vector<int2> chunks;
-      for (size_t k = 0; k < segs.size(); ++k)
-        for (int c = 0; c < segs[k].n; c += P2P_PULL_COLS) {
-          chunks.push_back(make_int2((int)k, c));
-          peers[segs[k].peer].nwg += 1;
-        }
-      pl.nchunk = (int)chunks.size();
-      pl.npeer_work = 0;
-      for (const P2PPeer& pr : peers) pl.npeer_work += pr.nwg ? 1 : 0;
-      if (ctx->loopback)  // the emulated readers of this rank: the peers with segments here
-        for (const P2PPeer& pr : peers)
-          if (pr.nwg) cons.push_back(pr.consumed);
-      if (cons.size() > 256 || ready.size() > 256) {
-        ctx->err = "MPAS_DYCORE_P2P: more than 256 peers";
-        return MPAS_DYC_EINVAL;
-      }
-      // [0] uses, [1] finished workgroups of k_p2p_pull, [2 + i] workgroups done for peer i
-      HIPCHK(hipMalloc(&pl.p2p_cnt, (2 + peers.size()) * sizeof(unsigned long long)));
-      HIPCHK(hipMemset(pl.p2p_cnt, 0, (2 + peers.size()) * sizeof(unsigned long long)));
-      for (size_t j = 0; j < peers.size(); ++j) peers[j].done = pl.p2p_cnt + 2 + j;
-      pl.npseg = (int)segs.size();
-      pl.nready = (int)ready.size();
-      pl.ncons = (int)cons.size();
-      pl.d_pseg = (P2PSeg*)upload(segs.data(), segs.size() * sizeof(P2PSeg));
-      pl.d_chunk = (int2*)upload(chunks.data(), chunks.size() * sizeof(int2));
-      pl.d_peer = (P2PPeer*)upload(peers.data(), peers.size() * sizeof(P2PPeer));
-      pl.d_ready = (unsigned long long**)upload(ready.data(), ready.size() * sizeof(void*));
-      pl.d_cons = (const unsigned long long**)upload(cons.data(), cons.size() * sizeof(void*));
-      if (!pl.d_pseg || !pl.d_chunk || !pl.d_peer || !pl.d_ready || !pl.d_cons) {
-        ctx->err = "hipMalloc for a pull plan failed";
-        return MPAS_DYC_EHIP;
-      }
-      // d_ready / d_cons are freed with the plan (free_plan); keep them out of pull_mem
-      pl.pull_mem.erase(std::remove_if(pl.pull_mem.begin(), pl.pull_mem.end(),
-                                       [&](void* q) { return q == (void*)pl.d_ready || q == (void*)pl.d_cons ||
-                                                             q == (void*)pl.d_pseg || q == (void*)pl.d_peer ||
-                                                             q == (void*)pl.d_chunk; }),
-                        pl.pull_mem.end());
-    }
-    return MPAS_DYC_OK;
-  }();
-  return nr > 1 ? p2p_vote(ctx, built, "mapping the peers' fields") : built;
-}
-
-// the one-sided transfer dropped on every rank (P2P_UNAVAILABLE): its mappings and arena freed, the
-// plans rebuilt for RCCL by the caller
-void p2p_fallback(mpas_dyc_ctx* ctx) {
-  fprintf(stderr, "mpas_dycore rank %d: %s; halo exchanges go through RCCL\n", ctx->rank, ctx->err.c_str());
-  invalidate_plans(ctx);
-  for (void* p : ctx->p2p_mapped) (void)hipIpcCloseMemHandle(p);
-  ctx->p2p_mapped.clear();
-  ctx->p2p_fields.clear();
-  if (ctx->p2p_flags) (void)hipFree(ctx->p2p_flags);
-  ctx->p2p_flags = nullptr;
-  ctx->p2p_peer_flags.clear();
-  ctx->p2p = 0;
-}
-
-// p2p_status: a wait of k_p2p_get that timed out
-int p2p_check(mpas_dyc_ctx* ctx) {
-  if (!ctx->p2p_status) return MPAS_DYC_OK;
-  int st = 0;
-  HIPCHK(hipMemcpy(&st, ctx->p2p_status, sizeof(int), hipMemcpyDeviceToHost));
-  if (st) {
-    ctx->err = std::string("MPAS_DYCORE_P2P: a peer's halo message did not arrive within 30 s (last exchange: ") +
-               ctx->last_key + ")";
-    return MPAS_DYC_ECOMM;
-  }
-  return MPAS_DYC_OK;
-}
+// one-sided transfer (MPAS_DYCORE_P2P, halo.hip): p2p_setup, p2p_fallback, p2p_teardown, p2p_check
+#include "p2p_setup.hip"
 
 // part: 0 the whole exchange; with one-sided transfer a split-phase exchange runs as 1 (pack and
 // post, at exchange_async) and 2 (get and unpack, at exchange_wait), all on the compute stream
@@ -3576,10 +2937,7 @@ void mpas_dyc_destroy(mpas_dyc_ctx* ctx) {
     if (b.sum_out) (void)hipFree(b.sum_out);
   }
   if (ctx->sum_gather) (void)hipFree(ctx->sum_gather);
-  for (void* p : ctx->p2p_mapped) (void)hipIpcCloseMemHandle(p);
-  if (ctx->p2p_flags) (void)hipFree(ctx->p2p_flags);
-  if (ctx->p2p_status) (void)hipFree(ctx->p2p_status);
-  if (ctx->p2p_status_host) (void)hipHostFree(ctx->p2p_status_host);
+  p2p_teardown(ctx);  // after the plans (invalidate_plans above) and the field buffers: see there
   if (ctx->comm) ncclCommDestroy(ctx->comm);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
