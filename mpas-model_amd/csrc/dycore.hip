@@ -483,6 +483,7 @@ Field* find(Block& b, const char* pool, const char* name) {
 }
 
 // state fields swap time levels every step; the lbc pool's two levels are fixed (tendency, state)
+bool swaps_levels(const Field& f) { return f.ntl == 2 && f.pool == "state"; }
 int slot_of(const mpas_dyc_ctx* c, const Field& f, int tl) {
   if (f.ntl == 2 && f.pool == "lbc") return tl == 2 ? 1 : 0;
   return (f.ntl == 2) ? ((tl == 2) ? 1 - c->cur : c->cur) : 0;
@@ -610,750 +611,12 @@ inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + WAVES_PER_BLOCK - 
       hipLaunchKernelGGL(kern, grid_for(n), dim3(BLOCK_THREADS), 0, ctx->stream, __VA_ARGS__);             \
   } while (0)
 
-// ---------------------------------------------------------------------------
-// halo exchange (mpas_dmpar_exch_halo_field, framework/mpas_dmpar.F)
-// ---------------------------------------------------------------------------
-bool needs_exchange(const mpas_dyc_ctx* ctx) { return ctx->blk.size() > 1 || ctx->nranks > 1 || ctx->loopback; }
-
-// An exchange plan holds the fields' buffers, so its key names them: the time level and, per field,
-// which of the buffers that the step's rotations move it is (buffer index of block 0)
-std::string plan_key(mpas_dyc_ctx* ctx, const std::vector<XField>& fs) {
-  std::string k = std::to_string(ctx->cur) + (ctx->plain_exchange ? "plain" : "");
-  for (const auto& f : fs) {
-    k += "|" + std::string(f.pool) + "." + f.name + "." + std::to_string(f.tl) + "." + std::to_string(f.layers);
-    Field* F = ctx->blk.empty() ? nullptr : find(ctx->blk[0], f.pool, f.name);
-    if (F && F->rot >= 0) k += "@" + std::to_string(F->rot_pos);
-    else if (F && F->ntl == 2 && F->pool == "state") k += "@" + std::to_string(slot_of(ctx, *F, f.tl) ^ F->flip);
-  }
-  return k;
-}
-
-const XList* find_list(const Block& b, int loc, int layer, int dir, int peer_rank, int peer_block) {
-  for (const auto& x : b.xl)
-    if (x.loc == loc && x.layer == layer && x.dir == dir && x.peer_rank == peer_rank && x.peer_block == peer_block)
-      return &x;
-  return nullptr;
-}
-
-// true if `key` contains one of the comma-separated substrings of `list` (a debugging switch's value)
-bool key_in_list(const char* list, const std::string& key) {
-  const std::string s = list ? list : "";
-  for (size_t a = 0; a < s.size();) {
-    size_t b = s.find(',', a);
-    if (b == std::string::npos) b = s.size();
-    if (b > a && key.find(s.substr(a, b - a)) != std::string::npos) return true;
-    a = b + 1;
-  }
-  return false;
-}
-
-// The one way a plan gets device memory: the allocation (at least 8 bytes) is recorded in pl.owned
-// the moment it exists, so free_plan frees it whatever fails later; `d` is a view.
-template <class T>
-int plan_alloc(mpas_dyc_ctx* ctx, XPlan& pl, T*& d, size_t bytes) {
-  void* p = nullptr;
-  HIPCHK(hipMalloc(&p, std::max<size_t>(bytes, 8)));
-  pl.owned.push_back(p);
-  d = (T*)p;
-  return MPAS_DYC_OK;
-}
-template <class T>
-int plan_upload(mpas_dyc_ctx* ctx, XPlan& pl, T*& d, const void* host, size_t bytes) {
-  CHK(plan_alloc(ctx, pl, d, bytes));
-  if (bytes) HIPCHK(hipMemcpy((void*)d, host, bytes, hipMemcpyHostToDevice));
-  return MPAS_DYC_OK;
-}
-
-void free_plan(XPlan& pl) {
-  for (void* p : pl.mapped) (void)hipIpcCloseMemHandle(p);
-  for (void* p : pl.owned) (void)hipFree(p);
-  pl = XPlan{};
-}
-
-// loopback: per emulated peer rank, its (send, receive) messages (either may be missing)
-std::map<int, std::pair<const XMsg*, const XMsg*>> loopback_pairs(const XPlan& pl) {
-  std::map<int, std::pair<const XMsg*, const XMsg*>> peers;
-  for (const XMsg& m : pl.rsend) peers[m.peer_rank].first = &m;
-  for (const XMsg& m : pl.rrecv) peers[m.peer_rank].second = &m;
-  return peers;
-}
-
 // captured steps bake pointers, list lengths and flags in: drop them when any of those changes
 void drop_graphs(mpas_dyc_ctx* ctx) {
   for (auto& kv : ctx->graphs)
     if (kv.second) (void)hipGraphExecDestroy(kv.second);
   ctx->graphs.clear();
   ctx->graph_dt.clear();
-}
-
-void invalidate_plans(mpas_dyc_ctx* ctx) {
-  if (!ctx->host_only) (void)hipStreamSynchronize(ctx->stream);
-  for (auto& kv : ctx->plans) free_plan(kv.second);
-  ctx->plans.clear();
-  ctx->planned.clear();
-  drop_graphs(ctx);
-}
-
-bool is_local(const mpas_dyc_ctx* ctx, int peer_rank) { return peer_rank == ctx->rank && !ctx->rccl_local; }
-
-std::vector<std::pair<int, int>> peers_of(const Block& b, int dir) {
-  std::vector<std::pair<int, int>> peers;
-  for (const auto& x : b.xl)
-    if (x.dir == dir && x.n > 0 && x.peer_block >= 0) peers.emplace_back(x.peer_rank, x.peer_block);
-  std::sort(peers.begin(), peers.end());
-  peers.erase(std::unique(peers.begin(), peers.end()), peers.end());
-  return peers;
-}
-
-inline bool batched(const Dims& d);
-inline bool pair_layout(const Dims& d);
-bool split_phase(const mpas_dyc_ctx* ctx);
-
-// Message layout: per block, peers in (rank, block) order; per peer, the fields in call
-// order and per field the halo layers in ascending order (both sides agree on it).
-int build_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, XPlan& pl) {
-  const int nb = (int)ctx->blk.size();
-  std::vector<XSeg> pre, post;
-  std::vector<int64_t> pre_off, post_off;  // buffer offsets, patched once the buffers exist (-1: direct)
-  std::vector<const std::vector<int32_t>*> pre_hidx;  // host send list of each block-pair pre segment
-  int64_t stotal = 0, rtotal = 0;
-  // the fused pack applies to the per-sub-step exchange (diag rtheta_pp [+ rho_pp], halo layer 1)
-  bool fusable = !fs.empty() && fs.size() <= 2 && !ctx->plain_exchange;
-  for (const auto& f : fs)
-    fusable = fusable && std::string(f.pool) == "diag" && f.layers == 0x1u &&
-              (std::string(f.name) == "rtheta_pp" || std::string(f.name) == "rho_pp");
-  struct PackSeg { int block, is_rho; const XList* sx; size_t seg; };
-  std::vector<PackSeg> pack_segs, unpack_segs;
-  // the 876-887 exchange (rw_p, ru_p, rho_pp all layers, rtheta_pp layer 2) is fused into the stage's
-  // last cell phase and damping (pack) and the halo recovery (unpack): XPack / XUnpack, dycore.h
-  std::function<int(const XField&)> rec_fid = [](const XField& f) -> int {
-    const std::string n(f.name);
-    if (std::string(f.pool) != "diag") return -1;
-    if (n == "rw_p" && (f.layers == ALL_LAYERS || f.layers == 0x1u)) return 0;  // 0x1: MPAS_DYCORE_HALO_TRIM
-    if (n == "rho_pp" && f.layers == ALL_LAYERS) return 1;
-    if (n == "rtheta_pp" && f.layers == 0x2u) return 2;
-    if (n == "ru_p" && f.layers == ALL_LAYERS) return 0;  // the edge field
-    return -1;
-  };
-  // 1: the 876-887 exchange; 2: the tend_u exchange (642), packed by the stage's final tend_u kernel
-  // (k_dyn_edges_p with finalize, k_dyn_edges_rk1b_b) and unpacked by k_smlstep_pert_b
-  int fkind = 0;
-  if (!ctx->plain_exchange && fs.size() == 4) {
-    fkind = 1;
-    for (const auto& f : fs) fkind = rec_fid(f) >= 0 ? fkind : 0;
-  } else if (!ctx->plain_exchange && fs.size() == 1 && std::string(fs[0].pool) == "tend" &&
-             std::string(fs[0].name) == "u" && fs[0].layers == 0x1u) {
-    fkind = 2;
-  } else if (!ctx->plain_exchange && !ctx->lbc && fs.size() == 1 && std::string(fs[0].pool) == "state" &&
-             std::string(fs[0].name) == "u" && fs[0].tl == 2 && fs[0].layers == ALL_LAYERS) {
-    fkind = 3;  // the u exchange after the recovery (988); regional runs overwrite u after the recovery
-  }
-  if (fkind >= 2) rec_fid = [](const XField&) -> int { return 0; };
-  bool recfuse = fkind != 0;
-  struct RecSeg { int block, fid; Loc loc; const XList* x; size_t seg; };
-  std::vector<RecSeg> rec_pack, rec_unpack;
-  auto field_of = [&](Block& b, const XField& f) -> Field* {
-    Field* F = find(b, f.pool, f.name);
-    if (!F || F->is_int || F->loc == L_NONE || (!F->buf[0] && !ctx->host_only)) {
-      ctx->err = std::string("halo exchange of unsupported field ") + f.pool + "." + f.name;
-      return nullptr;
-    }
-    return F;
-  };
-  for (int bi = 0; bi < nb; ++bi) {
-    Block& b = ctx->blk[bi];
-    for (const auto& pr : peers_of(b, MPAS_DYC_SEND)) {
-      const bool local = is_local(ctx, pr.first);
-      if (local && (pr.second < 0 || pr.second >= nb)) {
-        ctx->err = "exchange list names block " + std::to_string(pr.second) + " not in this process";
-        return MPAS_DYC_EINVAL;
-      }
-      const int64_t start = stotal;
-      for (const auto& f : fs) {
-        Field* F = field_of(b, f);
-        if (!F) return MPAS_DYC_EINVAL;
-        for (int layer = 1; layer <= 3; ++layer) {
-          if (!((f.layers >> (layer - 1)) & 1u)) continue;
-          const XList* sx = find_list(b, (int)F->loc, layer, MPAS_DYC_SEND, pr.first, pr.second);
-          if (!sx || sx->n == 0) continue;
-          const XList* rx = nullptr;
-          Field* PF = nullptr;
-          if (local) {
-            Block& pb = ctx->blk[pr.second];
-            rx = find_list(pb, (int)F->loc, layer, MPAS_DYC_RECV, ctx->rank, bi);
-            if (!rx || rx->n != sx->n) {
-              ctx->err = "send/recv lists of blocks " + std::to_string(bi) + "->" + std::to_string(pr.second) +
-                         " disagree";
-              return MPAS_DYC_EINVAL;
-            }
-            PF = find(pb, f.pool, f.name);
-          }
-          // a scalar-major field moves as nsub fields of inner/nsub doubles
-          const int64_t sub_inner = F->inner / F->nsub;
-          for (int is = 0; is < F->nsub; ++is) {
-            XSeg sg{};
-            sg.src = (const double*)F->buf[slot_of(ctx, *F, f.tl)] + (size_t)is * nloc(b, F->loc) * sub_inner;
-            sg.sidx = sx->d_idx;
-            sg.n = sx->n;
-            sg.inner = (int)sub_inner;
-            if (local) {
-              sg.dst = (double*)PF->buf[slot_of(ctx, *PF, f.tl)] + (size_t)is * nloc(ctx->blk[pr.second], PF->loc) * sub_inner;
-              sg.didx = rx->d_idx;
-              pre_off.push_back(-1);
-              fusable = false;  // a direct copy would reach the peer's halo before its cell phase reads it
-              recfuse = false;
-            } else {
-              sg.didx = nullptr;
-              pre_off.push_back(stotal);
-              stotal += (int64_t)sx->n * sub_inner;
-              if (fusable) pack_segs.push_back(PackSeg{bi, std::string(f.name) == "rho_pp" ? 1 : 0, sx, pre.size()});
-              if (recfuse) rec_pack.push_back(RecSeg{bi, rec_fid(f), F->loc, sx, pre.size()});
-            }
-            pre.push_back(sg);
-            pre_hidx.push_back(&sx->h_idx);
-          }
-          pl.maxn_pre = std::max(pl.maxn_pre, sx->n);
-        }
-      }
-      if (!local && stotal > start) pl.rsend.push_back(XMsg{bi, pr.first, pr.second, start, stotal - start});
-    }
-    for (const auto& pr : peers_of(b, MPAS_DYC_RECV)) {
-      const bool local = is_local(ctx, pr.first);
-      const int64_t start = rtotal;
-      for (const auto& f : fs) {
-        Field* F = field_of(b, f);
-        if (!F) return MPAS_DYC_EINVAL;
-        for (int layer = 1; layer <= 3; ++layer) {
-          if (!((f.layers >> (layer - 1)) & 1u)) continue;
-          const XList* rx = find_list(b, (int)F->loc, layer, MPAS_DYC_RECV, pr.first, pr.second);
-          if (!rx || rx->n == 0) continue;
-          if (local) {  // filled by the sender's direct copy; check that one exists
-            const XList* sx = (pr.second >= 0 && pr.second < nb)
-                                  ? find_list(ctx->blk[pr.second], (int)F->loc, layer, MPAS_DYC_SEND, ctx->rank, bi)
-                                  : nullptr;
-            if (!sx || sx->n != rx->n) {
-              ctx->err = "send/recv lists of blocks " + std::to_string(pr.second) + "->" + std::to_string(bi) +
-                         " disagree";
-              return MPAS_DYC_EINVAL;
-            }
-            continue;
-          }
-          const int64_t sub_inner = F->inner / F->nsub;
-          for (int is = 0; is < F->nsub; ++is) {
-            XSeg sg{};
-            sg.sidx = nullptr;
-            sg.dst = (double*)F->buf[slot_of(ctx, *F, f.tl)] + (size_t)is * nloc(b, F->loc) * sub_inner;
-            sg.didx = rx->d_idx;
-            sg.n = rx->n;
-            sg.inner = (int)sub_inner;
-            if (fusable) unpack_segs.push_back(PackSeg{bi, std::string(f.name) == "rho_pp" ? 1 : 0, rx, post.size()});
-            if (recfuse) rec_unpack.push_back(RecSeg{bi, rec_fid(f), F->loc, rx, post.size()});
-            post.push_back(sg);
-            post_off.push_back(rtotal);
-            rtotal += (int64_t)rx->n * sub_inner;
-          }
-          pl.maxn_post = std::max(pl.maxn_post, rx->n);
-        }
-      }
-      if (!local && rtotal > start) pl.rrecv.push_back(XMsg{bi, pr.first, pr.second, start, rtotal - start});
-    }
-  }
-  bool positional = false;
-  // positional lists (mpas_dyc_set_exchange_positions): per peer rank one message, laid out as
-  // mpas_dmpar lays out its buffer (mpas_dmpar.F:5448-5535): per field, per halo layer a region whose
-  // slots the blocks of this process fill at their positions; the receiver reads its blocks' slots
-  // at theirs.  Region sizes are the largest position over the blocks (both sides agree: it is one
-  // buffer).  No fused pack / unpack for them.
-  {
-    std::set<int> pos_ranks;
-    for (const auto& b : ctx->blk)
-      for (const auto& x : b.xl)
-        if (x.peer_block < 0 && x.n > 0) pos_ranks.insert(x.peer_rank);
-    for (int dir = MPAS_DYC_SEND; dir <= MPAS_DYC_RECV; ++dir)
-      for (int pr : pos_ranks) {
-        int64_t& total = dir == MPAS_DYC_SEND ? stotal : rtotal;
-        const int64_t start = total;
-        for (const auto& f : fs) {
-          Field* F0 = field_of(ctx->blk[0], f);
-          if (!F0) return MPAS_DYC_EINVAL;
-          for (int layer = 1; layer <= 3; ++layer) {
-            if (!((f.layers >> (layer - 1)) & 1u)) continue;
-            std::vector<const XList*> lx(nb, nullptr);
-            int64_t npos = 0;
-            for (int bi = 0; bi < nb; ++bi)
-              for (const auto& x : ctx->blk[bi].xl)
-                if (x.peer_block < 0 && x.n > 0 && x.peer_rank == pr && x.dir == dir && x.loc == (int)F0->loc &&
-                    x.layer == layer) {
-                  lx[bi] = &x;
-                  for (int32_t q : x.h_pos) npos = std::max<int64_t>(npos, (int64_t)q + 1);
-                }
-            if (!npos) continue;
-            const int64_t sub_inner = F0->inner / F0->nsub;
-            for (int is = 0; is < F0->nsub; ++is) {
-              for (int bi = 0; bi < nb; ++bi) {
-                if (!lx[bi]) continue;
-                Block& b = ctx->blk[bi];
-                Field* F = field_of(b, f);
-                if (!F) return MPAS_DYC_EINVAL;
-                double* fld = (double*)F->buf[slot_of(ctx, *F, f.tl)] + (size_t)is * nloc(b, F->loc) * sub_inner;
-                XSeg sg{};
-                sg.n = lx[bi]->n;
-                sg.inner = (int)sub_inner;
-                if (dir == MPAS_DYC_SEND) {
-                  sg.src = fld;
-                  sg.sidx = lx[bi]->d_idx;
-                  sg.didx = lx[bi]->d_pos;
-                  pre.push_back(sg);
-                  pre_off.push_back(total);
-                  pl.maxn_pre = std::max(pl.maxn_pre, sg.n);
-                } else {
-                  sg.sidx = lx[bi]->d_pos;
-                  sg.dst = fld;
-                  sg.didx = lx[bi]->d_idx;
-                  post.push_back(sg);
-                  post_off.push_back(total);
-                  pl.maxn_post = std::max(pl.maxn_post, sg.n);
-                }
-              }
-              total += npos * sub_inner;
-            }
-          }
-        }
-        if (total > start) (dir == MPAS_DYC_SEND ? pl.rsend : pl.rrecv).push_back(XMsg{-1, pr, -1, start, total - start});
-      }
-    if (!pos_ranks.empty()) {
-      positional = true;
-      fusable = false;
-      recfuse = false;
-      for (const auto& m : pl.rsend)
-        for (const auto& m2 : pl.rsend)
-          if (m.peer_rank == m2.peer_rank && (m.block < 0) != (m2.block < 0)) {
-            ctx->err = "rank " + std::to_string(m.peer_rank) + " has both positional and block-pair exchange lists";
-            return MPAS_DYC_EINVAL;
-          }
-    }
-  }
-  if ((!pl.rsend.empty() || !pl.rrecv.empty()) && !ctx->comm && !(ctx->host_allgather && ctx->p2p) &&
-      !ctx->host_only) {
-    ctx->err = "exchange lists name other processes but no communicator was set (mpas_dyc_comm_init)";
-    return MPAS_DYC_ECOMM;
-  }
-  // point-to-point messages between two ranks match in issue order: order both sides by
-  // (source block, destination block)
-  std::sort(pl.rsend.begin(), pl.rsend.end(), [](const XMsg& a, const XMsg& b) {
-    return std::make_tuple(a.peer_rank, a.block, a.peer_block) < std::make_tuple(b.peer_rank, b.block, b.peer_block);
-  });
-  std::sort(pl.rrecv.begin(), pl.rrecv.end(), [](const XMsg& a, const XMsg& b) {
-    return std::make_tuple(a.peer_rank, a.peer_block, a.block) < std::make_tuple(b.peer_rank, b.peer_block, b.block);
-  });
-  // One RCCL message per peer rank, as mpas_dmpar packs one buffer per processor for all its
-  // blocks (mpas_dmpar.F:5386-5552): the block-pair messages to one rank are laid out back to back
-  // in the order both sides sort them above, and go as one send / one receive.  (With one block
-  // per rank nothing changes; with several, e.g. bench.py --blocks B or --rccl-local, the group
-  // holds one message per peer rank instead of one per block pair.)
-  auto merge_by_rank = [](std::vector<XMsg>& msgs, std::vector<int64_t>& offs) {
-    std::map<int64_t, int64_t> base;  // message start, old layout -> new layout
-    int64_t cur = 0;
-    for (const XMsg& m : msgs) {
-      base[m.off] = cur;
-      cur += m.count;
-    }
-    for (int64_t& o : offs) {
-      if (o < 0) continue;  // a direct in-process copy
-      auto it = std::prev(base.upper_bound(o));
-      o = it->second + (o - it->first);
-    }
-    std::vector<XMsg> merged;
-    for (XMsg m : msgs) {
-      m.off = base[m.off];
-      if (!merged.empty() && merged.back().peer_rank == m.peer_rank) {
-        merged.back().count += m.count;
-        merged.back().block = merged.back().peer_block = -1;  // several block pairs
-      } else {
-        merged.push_back(m);
-      }
-    }
-    msgs.swap(merged);
-  };
-  merge_by_rank(pl.rsend, pre_off);
-  merge_by_rank(pl.rrecv, post_off);
-  if (ctx->host_only) return MPAS_DYC_OK;  // the dry run keeps the message lists only
-  if (ctx->loopback) stotal = rtotal = stotal + rtotal;  // rccl_group's loopback pairs stay inside
-  // with other ranks, every exchange point is a one-sided one on every rank, messages or not: the
-  // set-up numbers the exchange points in the same order on every rank (flag indices, records)
-  pl.p2p = ctx->p2p && (!pl.rsend.empty() || !pl.rrecv.empty() || ctx->nranks > 1);
-  pl.pull = pl.p2p && ctx->p2p_pull && !positional && !split_phase(ctx);
-  // debugging: MPAS_DYCORE_P2P_BUFFERS names exchange points (key substrings) to run in buffers mode
-  if (pl.pull && key_in_list(getenv("MPAS_DYCORE_P2P_BUFFERS"), plan_key(ctx, fs))) pl.pull = false;
-  if (pl.pull) {
-    // the receiver copies from the fields: no buffers, and the kernels store and read the fields
-    // themselves (no fused pack / unpack)
-    fusable = recfuse = false;
-    pl.h_pre = pre;
-    pl.h_pre_off = pre_off;
-    pl.h_pre_idx = pre_hidx;
-    pl.h_post = post;
-    pl.h_post_off = post_off;
-    std::vector<XSeg> loc;
-    for (size_t i = 0; i < pre.size(); ++i)
-      if (pre_off[i] < 0) {
-        loc.push_back(pre[i]);
-        pl.maxn_local = std::max(pl.maxn_local, pre[i].n);
-      }
-    pl.nlocal = (int)loc.size();
-    if (pl.nlocal) CHK(plan_upload(ctx, pl, pl.d_local, loc.data(), loc.size() * sizeof(XSeg)));
-    return MPAS_DYC_OK;
-  }
-  if (pl.p2p) {
-    // read by the peers (IPC): ordinary device memory, as the fields a pull reads -- the producer's
-    // stores reach memory when its kernel ends (the L2 write-back that makes them visible to the
-    // other XCDs), and the peers load it with system-scope loads (an uncached allocation here was
-    // read stale by a peer process now and then: halo.hip)
-    CHK(plan_alloc(ctx, pl, pl.sendbuf, std::max<int64_t>(stotal, 1) * sizeof(double) + 256));
-  } else if (stotal) {
-    CHK(plan_alloc(ctx, pl, pl.sendbuf, stotal * sizeof(double)));
-  }
-  // 256 B of slack: a fused unpack (ld_pp) reads the two levels of its lane's pair, one past the
-  // last column at an odd K
-  if (rtotal) CHK(plan_alloc(ctx, pl, pl.recvbuf, rtotal * sizeof(double) + 256));
-  for (size_t i = 0; i < pre.size(); ++i)
-    if (pre_off[i] >= 0) pre[i].dst = pl.sendbuf + pre_off[i];
-  for (size_t i = 0; i < post.size(); ++i) post[i].src = pl.recvbuf + post_off[i];
-  pl.npre = (int)pre.size();
-  pl.npost = (int)post.size();
-  if (fusable && !pack_segs.empty()) {
-    for (int bi = 0; bi < nb; ++bi) fusable = fusable && batched(ctx->blk[bi].d);
-  }
-  if (fusable && !pack_segs.empty()) {
-    // per block: CSR over owned cells of (rtheta_pp slot, rho_pp slot) pairs; a cell has one
-    // slot per RCCL peer that needs it (element i of a peer's list in both fields' segments)
-    const bool with_rho = fs.size() == 2;
-    pl.pack.assign(nb, PackMap{});
-    for (int bi = 0; bi < nb; ++bi) {
-      const Dims& d = ctx->blk[bi].d;
-      std::map<std::pair<const XList*, int>, std::pair<double*, double*>> slot;  // (list, i) -> (rt, rho)
-      for (const PackSeg& ps : pack_segs) {
-        if (ps.block != bi) continue;
-        for (int i = 0; i < ps.sx->n; ++i) {
-          double* col = pre[ps.seg].dst + (size_t)i * pre[ps.seg].inner;
-          auto& e = slot[{ps.sx, i}];
-          (ps.is_rho ? e.second : e.first) = col;
-        }
-      }
-      std::vector<std::vector<std::pair<double*, double*>>> per_cell(d.nCellsSolve);
-      for (const auto& kv : slot) per_cell[kv.first.first->h_idx[kv.first.second]].push_back(kv.second);
-      std::vector<int> start(d.nCellsSolve + 1, 0);
-      std::vector<double*> rt, rho;
-      for (int c = 0; c < d.nCellsSolve; ++c) {
-        start[c] = (int)rt.size();
-        for (const auto& e : per_cell[c]) {
-          rt.push_back(e.first);
-          rho.push_back(e.second);
-        }
-      }
-      start[d.nCellsSolve] = (int)rt.size();
-      if (rt.empty()) continue;
-      PackMap& pm = pl.pack[bi];
-      CHK(plan_upload(ctx, pl, pm.start, start.data(), start.size() * sizeof(int)));
-      CHK(plan_upload(ctx, pl, pm.rt, rt.data(), rt.size() * sizeof(double*)));
-      if (with_rho) CHK(plan_upload(ctx, pl, pm.rho, rho.data(), rho.size() * sizeof(double*)));
-    }
-    pl.fused_pack = ctx->fused_pack_enabled;
-    // unpack maps: halo cell -> its columns in the receive buffer (consumers: pair kernels only)
-    bool pair_all = true;
-    for (int bi = 0; bi < nb; ++bi) pair_all = pair_all && pair_layout(ctx->blk[bi].d);
-    if (pair_all && !unpack_segs.empty() && ctx->fused_pack_enabled) {
-      pl.unpack.assign(nb, UnpackMap{});
-      for (int bi = 0; bi < nb; ++bi) {
-        const Dims& d = ctx->blk[bi].d;
-        const int nh = d.nCells - d.nCellsSolve;
-        std::vector<int> rt(nh, -1), rho(nh, -1);
-        bool any = false;
-        for (const PackSeg& ps : unpack_segs) {
-          if (ps.block != bi) continue;
-          for (int i = 0; i < ps.sx->n; ++i) {
-            const int64_t off = (int64_t)(post[ps.seg].src - pl.recvbuf) + (int64_t)i * post[ps.seg].inner;
-            (ps.is_rho ? rho : rt)[ps.sx->h_idx[i] - d.nCellsSolve] = (int)off;
-            any = true;
-          }
-        }
-        if (!any) continue;
-        UnpackMap& um = pl.unpack[bi];
-        um.recv = pl.recvbuf;
-        CHK(plan_upload(ctx, pl, um.rt, rt.data(), nh * sizeof(int)));
-        if (with_rho) CHK(plan_upload(ctx, pl, um.rho, rho.data(), nh * sizeof(int)));
-      }
-      pl.fused_unpack = true;
-    }
-  }
-  if (recfuse && (!rec_pack.empty() || !rec_unpack.empty()) && ctx->fused_pack_enabled) {
-    bool pair_all = true;
-    for (int bi = 0; bi < nb; ++bi) pair_all = pair_all && pair_layout(ctx->blk[bi].d);
-    if (pair_all) {
-      pl.rpk_cell.assign(nb, XPack{});
-      pl.rpk_edge.assign(nb, XPack{});
-      pl.rup_cell.assign(nb, XUnpack{});
-      pl.rup_edge.assign(nb, XUnpack{});
-      for (int bi = 0; bi < nb; ++bi) {
-        const Dims& d = ctx->blk[bi].d;
-        for (const Loc loc : {L_CELL, L_EDGE}) {
-          const int nsolve = loc == L_CELL ? d.nCellsSolve : d.nEdgesSolve;
-          const int nh = (loc == L_CELL ? d.nCells : d.nEdges) - nsolve;
-          const int nf = loc == L_CELL ? 3 : 1;
-          // pack: per owned element, (field, send-buffer column) slots in element order
-          std::vector<std::vector<std::pair<int, double*>>> per(nsolve);
-          for (const RecSeg& rs : rec_pack) {
-            if (rs.block != bi || rs.loc != loc) continue;
-            for (int i = 0; i < rs.x->n; ++i)
-              per[rs.x->h_idx[i]].emplace_back(rs.fid, pre[rs.seg].dst + (size_t)i * pre[rs.seg].inner);
-          }
-          std::vector<int> start(nsolve + 1, 0), fid;
-          std::vector<double*> dst;
-          for (int i = 0; i < nsolve; ++i) {
-            start[i] = (int)fid.size();
-            for (const auto& sl : per[i]) {
-              fid.push_back(sl.first);
-              dst.push_back(sl.second);
-            }
-          }
-          start[nsolve] = (int)fid.size();
-          if (!fid.empty()) {
-            XPack& xp = (loc == L_CELL ? pl.rpk_cell : pl.rpk_edge)[bi];
-            CHK(plan_upload(ctx, pl, xp.start, start.data(), start.size() * sizeof(int)));
-            CHK(plan_upload(ctx, pl, xp.fid, fid.data(), fid.size() * sizeof(int)));
-            CHK(plan_upload(ctx, pl, xp.dst, dst.data(), dst.size() * sizeof(double*)));
-          }
-          // unpack: per field and halo element, its column in the receive buffer
-          std::vector<int> off((size_t)nf * std::max(nh, 0), -1);
-          bool any = false;
-          for (const RecSeg& rs : rec_unpack) {
-            if (rs.block != bi || rs.loc != loc) continue;
-            for (int i = 0; i < rs.x->n; ++i) {
-              off[(size_t)rs.fid * nh + (rs.x->h_idx[i] - nsolve)] =
-                  (int)((post[rs.seg].src - pl.recvbuf) + (int64_t)i * post[rs.seg].inner);
-              any = true;
-            }
-          }
-          const int* d_wb = nullptr;
-          if (any && fkind == 3) {
-            // each received halo edge is written back by one vertex of the block that has it among its
-            // edgesOnVertex (the vertex kernel is its first reader); an edge without one: no fusion
-            const Block& b = ctx->blk[bi];
-            std::vector<int> wb(std::max(nh, 0), -1);
-            bool ok = (int64_t)b.h_voe.size() >= 2LL * d.nEdges && (int64_t)b.h_eov.size() >= 3LL * d.nVertices;
-            for (int i = 0; ok && i < nh; ++i) {
-              if (off[i] < 0) continue;
-              const int e = nsolve + i;
-              for (int j = 0; j < 2 && wb[i] < 0; ++j) {
-                const int v = b.h_voe[2 * (size_t)e + j];
-                if (v < 0 || v >= d.nVertices) continue;
-                for (int m = 0; m < 3; ++m)
-                  if (b.h_eov[3 * (size_t)v + m] == e) wb[i] = v;
-              }
-              ok = wb[i] >= 0;
-            }
-            if (!ok) {
-              recfuse = false;
-              break;
-            }
-            CHK(plan_upload(ctx, pl, d_wb, wb.data(), wb.size() * sizeof(int)));
-          }
-          if (any) {
-            const int* doff = nullptr;
-            CHK(plan_upload(ctx, pl, doff, off.data(), off.size() * sizeof(int)));
-            (loc == L_CELL ? pl.rup_cell : pl.rup_edge)[bi] = XUnpack{pl.recvbuf, doff, nh, d_wb};
-          }
-        }
-      }
-      if (recfuse) {
-        pl.fused_rec = fkind;
-        pl.fused_pack = pl.fused_unpack = true;
-      } else {  // a write-back vertex is missing: the pack / unpack kernels run (maps unused)
-        pl.rpk_cell.clear();
-        pl.rpk_edge.clear();
-        pl.rup_cell.clear();
-        pl.rup_edge.clear();
-      }
-    }
-  }
-  if (pl.npre) CHK(plan_upload(ctx, pl, pl.d_pre, pre.data(), pre.size() * sizeof(XSeg)));
-  if (pl.npost) CHK(plan_upload(ctx, pl, pl.d_post, post.data(), post.size() * sizeof(XSeg)));
-  return MPAS_DYC_OK;
-}
-
-// a profile event pair's first half on `s` (the second is prof_mark_end); nothing unless profiling
-int prof_mark(mpas_dyc_ctx* ctx, std::vector<hipEvent_t>& v, hipStream_t s) {
-  if (!ctx->profile || ctx->planning) return MPAS_DYC_OK;
-  hipEvent_t e = nullptr;
-  HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(e, s));
-  v.push_back(e);
-  return MPAS_DYC_OK;
-}
-
-void set_last_key(mpas_dyc_ctx* ctx, const std::string& k) {
-  const size_t n = std::min(k.size(), sizeof(ctx->last_key) - 1);
-  memcpy(ctx->last_key, k.data(), n);
-  ctx->last_key[n] = 0;
-}
-
-// The RCCL group of an exchange: one send and one receive per peer rank.  Loopback (timing
-// emulation): each peer's pair goes to this rank itself; a send to self and the receive that
-// matches it must have one size, so both move min(send, receive) doubles.
-int rccl_group(mpas_dyc_ctx* ctx, const XPlan& pl) {
-  NCCLCHK(ncclGroupStart());
-  if (ctx->loopback) {
-    // one self pair per peer rank of max(send, receive) doubles (a peer this rank only sends to or
-    // only receives from gets one too); build_plan sizes both buffers for it
-    for (const auto& kv : loopback_pairs(pl)) {
-      const XMsg *sm = kv.second.first, *rm = kv.second.second;
-      const size_t n = (size_t)std::max(sm ? sm->count : 0, rm ? rm->count : 0);
-      if (ctx->loopback == 2) {
-        HIPCHK(hipMemcpyAsync(pl.recvbuf + (rm ? rm->off : 0), pl.sendbuf + (sm ? sm->off : 0), n * sizeof(double),
-                              hipMemcpyDeviceToDevice, ctx->stream));
-        continue;
-      }
-      NCCLCHK(ncclSend(pl.sendbuf + (sm ? sm->off : 0), n, ncclFloat64, ctx->rank, ctx->comm, ctx->stream));
-      NCCLCHK(ncclRecv(pl.recvbuf + (rm ? rm->off : 0), n, ncclFloat64, ctx->rank, ctx->comm, ctx->stream));
-    }
-  } else {
-    for (const XMsg& m : pl.rsend)
-      NCCLCHK(ncclSend(pl.sendbuf + m.off, (size_t)m.count, ncclFloat64, m.peer_rank, ctx->comm, ctx->stream));
-    for (const XMsg& m : pl.rrecv)
-      NCCLCHK(ncclRecv(pl.recvbuf + m.off, (size_t)m.count, ncclFloat64, m.peer_rank, ctx->comm, ctx->stream));
-  }
-  NCCLCHK(ncclGroupEnd());
-  return MPAS_DYC_OK;
-}
-
-// one-sided transfer (MPAS_DYCORE_P2P, halo.hip): p2p_setup, p2p_fallback, p2p_teardown, p2p_check
-#include "p2p_setup.hip"
-
-// part: 0 the whole exchange; with one-sided transfer a split-phase exchange runs as 1 (pack and
-// post, at exchange_async) and 2 (get and unpack, at exchange_wait), all on the compute stream
-int exchange(mpas_dyc_ctx* ctx, const std::vector<XField>& fs, int part = 0) {
-  if (!needs_exchange(ctx)) return MPAS_DYC_OK;
-  const std::string key = plan_key(ctx, fs);
-  if (ctx->record) ctx->record->push_back(key);
-  auto it = ctx->plans.find(key);
-  if (it == ctx->plans.end()) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (!ctx->host_only) (void)hipStreamIsCapturing(ctx->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) {
-      ctx->err = "internal: exchange plan missing during graph capture";
-      return MPAS_DYC_ESTATE;
-    }
-    XPlan pl;
-    int r = build_plan(ctx, fs, pl);
-    if (r) {
-      free_plan(pl);
-      return r;
-    }
-    it = ctx->plans.emplace(key, std::move(pl)).first;
-  }
-  if (ctx->planning) return MPAS_DYC_OK;
-  XPlan& pl = it->second;
-  if (pl.p2p) {
-    if (pl.p2p_id < 0) {  // built outside plan_all (mpas_dyc_halo_exchange): every rank is here too
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      (void)hipStreamIsCapturing(ctx->stream, &cs);
-      if (cs != hipStreamCaptureStatusNone) {
-        ctx->err = "internal: one-sided exchange set up during graph capture";
-        return MPAS_DYC_ESTATE;
-      }
-      const int r = p2p_setup(ctx);
-      if (r == P2P_UNAVAILABLE) {  // every rank is here: this exchange, and the rest, through RCCL
-        if (!ctx->comm) return MPAS_DYC_ECOMM;
-        p2p_fallback(ctx);
-        return exchange(ctx, fs, part);
-      }
-      CHK(r);
-    }
-    if (pl.pull) {  // blocking only (build_plan): the whole exchange at the first call
-      if (part == 2) return MPAS_DYC_OK;
-      CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));
-      if (pl.nlocal)
-        hipLaunchKernelGGL(k_halo_copy, dim3((pl.maxn_local + 3) / 4, pl.nlocal), dim3(256), 0, ctx->stream, pl.d_local);
-      set_last_key(ctx, key);
-      CHK(prof_mark(ctx, ctx->prof_rccl, ctx->stream));
-      hipLaunchKernelGGL(k_p2p_pull, dim3(pl.nchunk + 1), dim3(256), 0, ctx->stream, (const P2PSeg*)pl.d_pseg,
-                         (const int2*)pl.d_chunk, pl.nchunk, (const P2PPeer*)pl.d_peer, pl.npeer_work,
-                         (unsigned long long* const*)pl.d_ready, pl.nready, (const unsigned long long* const*)pl.d_cons,
-                         pl.ncons, pl.p2p_cnt, ctx->p2p_status, ctx->p2p_release);
-      CHK(prof_mark(ctx, ctx->prof_rccl, ctx->stream));
-      CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));
-      return MPAS_DYC_OK;
-    }
-    if (part == 0 && !ctx->p2p_merge) {  // the two launches (A/B of the merged one)
-      CHK(exchange(ctx, fs, 1));
-      return exchange(ctx, fs, 2);
-    }
-    if (part == 0) {  // blocking: post and get as one launch (k_p2p_exchange)
-      CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));
-      if (pl.npre && !pl.fused_pack)
-        hipLaunchKernelGGL(k_halo_copy, dim3((pl.maxn_pre + 3) / 4, pl.npre), dim3(256), 0, ctx->stream, pl.d_pre);
-      set_last_key(ctx, key);
-      CHK(prof_mark(ctx, ctx->prof_rccl, ctx->stream));
-      hipLaunchKernelGGL(k_p2p_exchange, dim3(std::max(pl.get_chunks, 1), pl.nget + 1), dim3(256), 0, ctx->stream,
-                         (const P2PGet*)pl.d_get, pl.nget, (unsigned long long* const*)pl.d_ready, pl.nready,
-                         (const unsigned long long* const*)pl.d_cons, pl.ncons, pl.p2p_cnt, ctx->p2p_status,
-                         ctx->p2p_release);
-      CHK(prof_mark(ctx, ctx->prof_rccl, ctx->stream));
-      if (pl.npost && !pl.fused_unpack)
-        hipLaunchKernelGGL(k_halo_copy, dim3((pl.maxn_post + 3) / 4, pl.npost), dim3(256), 0, ctx->stream, pl.d_post);
-      CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));
-      return MPAS_DYC_OK;
-    }
-    if (part == 1) {
-      if (pl.npre && !pl.fused_pack)
-        hipLaunchKernelGGL(k_halo_copy, dim3((pl.maxn_pre + 3) / 4, pl.npre), dim3(256), 0, ctx->stream, pl.d_pre);
-      set_last_key(ctx, key);
-      hipLaunchKernelGGL(k_p2p_post, dim3(1), dim3(64), 0, ctx->stream, pl.p2p_cnt, pl.d_ready, pl.nready,
-                         ctx->p2p_release);
-    }
-    if (part != 1) {
-      CHK(prof_mark(ctx, ctx->prof_rccl, ctx->stream));
-      hipLaunchKernelGGL(k_p2p_get, dim3(std::max(pl.get_chunks, 1), pl.nget + 1), dim3(256), 0, ctx->stream,
-                         (const P2PGet*)pl.d_get, pl.nget, (const unsigned long long* const*)pl.d_cons, pl.ncons,
-                         (const unsigned long long*)pl.p2p_cnt, ctx->p2p_status);
-      CHK(prof_mark(ctx, ctx->prof_rccl, ctx->stream));
-      if (pl.npost && !pl.fused_unpack)
-        hipLaunchKernelGGL(k_halo_copy, dim3((pl.maxn_post + 3) / 4, pl.npost), dim3(256), 0, ctx->stream, pl.d_post);
-    }
-    return MPAS_DYC_OK;
-  }
-  if (part == 2) return MPAS_DYC_OK;  // in-process copies only: done at part 1
-  const bool whole = !ctx->in_async;  // a blocking exchange: all of it is exposed
-  if (whole) CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));
-  if (pl.npre && !pl.fused_pack)
-    hipLaunchKernelGGL(k_halo_copy, dim3((pl.maxn_pre + 3) / 4, pl.npre), dim3(256), 0, ctx->stream, pl.d_pre);
-  if (!pl.rsend.empty() || !pl.rrecv.empty()) {
-    set_last_key(ctx, key);
-    CHK(prof_mark(ctx, ctx->prof_rccl, ctx->stream));
-    CHK(rccl_group(ctx, pl));
-    CHK(prof_mark(ctx, ctx->prof_rccl, ctx->stream));
-  }
-  if (pl.npost && !pl.fused_unpack)
-    hipLaunchKernelGGL(k_halo_copy, dim3((pl.maxn_post + 3) / 4, pl.npost), dim3(256), 0, ctx->stream, pl.d_post);
-  if (whole) CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));
-  return MPAS_DYC_OK;
-}
-
-// The plan of an exchange whose pack the producing kernel does (XPlan::fused_pack), or nullptr
-const XPlan* fused_pack_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs) {
-  if (ctx->planning || !needs_exchange(ctx)) return nullptr;
-  auto it = ctx->plans.find(plan_key(ctx, fs));
-  if (it == ctx->plans.end() || !it->second.fused_pack || it->second.pack.size() != ctx->blk.size()) return nullptr;
-  return &it->second;
-}
-
-// The plan of the 876-887 or 642 exchange when its pack and unpack are fused (XPlan::fused_rec), or
-// nullptr
-const XPlan* fused_rec_plan(mpas_dyc_ctx* ctx, const std::vector<XField>& fs) {
-  if (ctx->planning || !needs_exchange(ctx)) return nullptr;
-  auto it = ctx->plans.find(plan_key(ctx, fs));
-  if (it == ctx->plans.end() || !it->second.fused_rec || it->second.rpk_cell.size() != ctx->blk.size()) return nullptr;
-  return &it->second;
 }
 
 // Kernel families: 0 "general" (one column per wave, loads where used -- any mesh), 1 "batched"
@@ -1401,6 +664,10 @@ std::string lbc_layout_error(const Dims& d) {
   return "regional LBCs need cells of at most 7 edges (max(nEdgesOnCell) = " + std::to_string(d.maxEdges) +
          ") and maxEdges2 >= " + std::to_string(2 * d.maxEdges - 2);
 }
+
+// halo exchange: the planner (classify, layout, bind, fused maps), exchange() and the split-phase
+// helpers; it includes p2p_setup.hip
+#include "exchange.hip"
 
 // The kernels index the maxEdges-strided mesh arrays with the mesh's actual cell degree, not with
 // the declared one.  maxEdges in a mesh file is "the largest number of neighbors that a primal mesh
@@ -1530,65 +797,6 @@ int compute_bnd(mpas_dyc_ctx* ctx) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   ctx->bnd_ready = true;
-  return MPAS_DYC_OK;
-}
-
-// Auto mode splits only when halo traffic goes through RCCL: block-to-block copies inside
-// one GPU are a single short kernel, and splitting them only adds launches.
-bool split_phase(const mpas_dyc_ctx* ctx) {
-  if (!needs_exchange(ctx)) return false;
-  if (ctx->overlap >= 0) return ctx->overlap != 0;
-  if (ctx->p2p) return false;  // the transfer is the receiver's kernel: nothing to overlap it with
-  return ctx->nranks > 1 || ctx->rccl_local || ctx->loopback;
-}
-
-// First half of a split-phase exchange: after everything queued on the compute stream,
-// the exchange stream packs, talks RCCL and unpacks; exchange_wait joins it back.
-int issue_async(mpas_dyc_ctx* ctx, const std::vector<XField>& fs) {
-  HIPCHK(hipStreamWaitEvent(ctx->xstream, ctx->xfork, 0));
-  hipStream_t s = ctx->stream;
-  ctx->stream = ctx->xstream;  // exchange() issues on ctx->stream
-  ctx->in_async = true;
-  const int r = exchange(ctx, fs);
-  ctx->in_async = false;
-  ctx->stream = s;
-  if (r) return r;
-  HIPCHK(hipEventRecord(ctx->xjoin, ctx->xstream));
-  return MPAS_DYC_OK;
-}
-
-int exchange_async(mpas_dyc_ctx* ctx, const std::vector<XField>& fs) {
-  if (ctx->planning) return exchange(ctx, fs);
-  if (ctx->p2p) {  // no second stream: pack and post now, the get at exchange_wait
-    ctx->p2p_open = fs;
-    ctx->p2p_pending = true;
-    return exchange(ctx, fs, 1);
-  }
-  HIPCHK(hipEventRecord(ctx->xfork, ctx->stream));
-  if (ctx->late_issue) {
-    ctx->late_fs = fs;
-    ctx->late_pending = true;
-    return MPAS_DYC_OK;
-  }
-  return issue_async(ctx, fs);
-}
-
-int exchange_wait(mpas_dyc_ctx* ctx) {
-  if (ctx->planning) return MPAS_DYC_OK;
-  if (ctx->p2p_pending) {
-    ctx->p2p_pending = false;
-    CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));
-    CHK(exchange(ctx, ctx->p2p_open, 2));
-    CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));
-    return MPAS_DYC_OK;
-  }
-  if (ctx->late_pending) {
-    ctx->late_pending = false;
-    CHK(issue_async(ctx, ctx->late_fs));
-  }
-  CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));  // the compute stream's work before the join
-  HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->xjoin, 0));
-  CHK(prof_mark(ctx, ctx->prof_exposed, ctx->stream));  // ... completes once the join has
   return MPAS_DYC_OK;
 }
 
@@ -2697,6 +1905,33 @@ Block* get_block(mpas_dyc_ctx* ctx, int32_t block) {
   return &ctx->blk[block];
 }
 
+// What mpas_dyc_set_exchange_list and _positions share.  A list's 0-based element index: senders
+// send owned elements; receivers fill halo elements
+bool list_index_ok(const Block& b, int location, int direction, int32_t v) {
+  const Dims& d = b.d;
+  const int64_t nl = location == MPAS_DYC_CELL ? d.nCells : location == MPAS_DYC_EDGE ? d.nEdges : d.nVertices;
+  const int64_t nown = location == MPAS_DYC_CELL ? d.nCellsSolve
+                       : location == MPAS_DYC_EDGE ? d.nEdgesSolve : d.nVerticesSolve;
+  return direction == MPAS_DYC_SEND ? (v >= 0 && v < nown) : (v >= nown && v < nl);
+}
+// the block's list of this key, appended if new
+XList& list_entry(Block& b, int loc, int layer, int dir, int peer_rank, int peer_block) {
+  if (const XList* x = find_list(b, loc, layer, dir, peer_rank, peer_block)) return const_cast<XList&>(*x);
+  b.xl.push_back(XList{loc, layer, dir, peer_rank, peer_block});
+  return b.xl.back();
+}
+// a list's device copy `d`, replaced by `h` (none in a host-only context, null for an empty list)
+int upload_list(mpas_dyc_ctx* ctx, int*& d, const std::vector<int32_t>& h) {
+  if (ctx->host_only) return MPAS_DYC_OK;
+  if (d) HIPCHK(hipFree(d));
+  d = nullptr;
+  if (h.empty()) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMalloc(&d, h.size() * sizeof(int32_t)));
+  HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  return MPAS_DYC_OK;
+}
+
 // edges with at least one owned cell (the acoustic edge loop's active set), from MPAS 1-based cellsOnEdge
 void count_active_edges(Block& b, const int32_t* coe) {
   int64_t n = 0;
@@ -3157,43 +2392,19 @@ int mpas_dyc_set_exchange_list(mpas_dyc_ctx* ctx, int32_t block, int32_t locatio
     ctx->err = "invalid exchange list arguments";
     return MPAS_DYC_EINVAL;
   }
-  Block& b = *bp;
-  const int64_t nl = location == MPAS_DYC_CELL ? b.d.nCells : location == MPAS_DYC_EDGE ? b.d.nEdges : b.d.nVertices;
-  const int64_t nown = location == MPAS_DYC_CELL ? b.d.nCellsSolve
-                       : location == MPAS_DYC_EDGE ? b.d.nEdgesSolve : b.d.nVerticesSolve;
   std::vector<int32_t> idx(n);
   for (int i = 0; i < n; ++i) {
-    const int32_t v = local_index[i] - 1;
-    // senders send owned elements; receivers fill halo elements
-    const bool ok = direction == MPAS_DYC_SEND ? (v >= 0 && v < nown) : (v >= nown && v < nl);
-    if (!ok) {
+    idx[i] = local_index[i] - 1;
+    if (!list_index_ok(*bp, location, direction, idx[i])) {
       ctx->err = "exchange list index " + std::to_string(local_index[i]) + " out of range";
       return MPAS_DYC_EINVAL;
     }
-    idx[i] = v;
   }
   invalidate_plans(ctx);
-  XList* x = nullptr;
-  for (auto& e : b.xl)
-    if (e.loc == location && e.layer == halo_layer && e.dir == direction && e.peer_rank == peer_rank &&
-        e.peer_block == peer_block)
-      x = &e;
-  if (!x) {
-    b.xl.push_back(XList{location, halo_layer, direction, peer_rank, peer_block});
-    x = &b.xl.back();
-  }
-  if (x->d_idx && !ctx->host_only) {
-    HIPCHK(hipFree(x->d_idx));
-    x->d_idx = nullptr;
-  }
-  x->n = n;
-  x->h_idx = idx;
-  if (n > 0 && !ctx->host_only) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMalloc(&x->d_idx, n * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(x->d_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  return MPAS_DYC_OK;
+  XList& x = list_entry(*bp, location, halo_layer, direction, peer_rank, peer_block);
+  x.n = n;
+  x.h_idx = idx;
+  return upload_list(ctx, x.d_idx, x.h_idx);
 }
 
 int mpas_dyc_set_exchange_positions(mpas_dyc_ctx* ctx, int32_t block, int32_t location, int32_t halo_layer,
@@ -3214,49 +2425,24 @@ int mpas_dyc_set_exchange_positions(mpas_dyc_ctx* ctx, int32_t block, int32_t lo
     ctx->err = "positional lists are for other ranks (mpas_dyc_set_exchange_list copies within a process)";
     return MPAS_DYC_EINVAL;
   }
-  Block& b = *bp;
-  const int64_t nl = location == MPAS_DYC_CELL ? b.d.nCells : location == MPAS_DYC_EDGE ? b.d.nEdges : b.d.nVertices;
-  const int64_t nown = location == MPAS_DYC_CELL ? b.d.nCellsSolve
-                       : location == MPAS_DYC_EDGE ? b.d.nEdgesSolve : b.d.nVerticesSolve;
   std::vector<int32_t> idx(n), pos(n);
   std::set<int32_t> seen;
   for (int i = 0; i < n; ++i) {
-    const int32_t v = local_index[i] - 1;
-    const bool ok = direction == MPAS_DYC_SEND ? (v >= 0 && v < nown) : (v >= nown && v < nl);
-    if (!ok || position[i] < 1 || !seen.insert(position[i]).second) {
+    idx[i] = local_index[i] - 1;
+    if (!list_index_ok(*bp, location, direction, idx[i]) || position[i] < 1 || !seen.insert(position[i]).second) {
       ctx->err = "exchange list entry " + std::to_string(i + 1) + " (index " + std::to_string(local_index[i]) +
                  ", position " + std::to_string(position[i]) + ") out of range or repeated";
       return MPAS_DYC_EINVAL;
     }
-    idx[i] = v;
     pos[i] = position[i] - 1;
   }
   invalidate_plans(ctx);
-  XList* x = nullptr;
-  for (auto& e : b.xl)
-    if (e.loc == location && e.layer == halo_layer && e.dir == direction && e.peer_rank == peer_rank &&
-        e.peer_block < 0)
-      x = &e;
-  if (!x) {
-    b.xl.push_back(XList{location, halo_layer, direction, peer_rank, -1});
-    x = &b.xl.back();
-  }
-  if (!ctx->host_only) {
-    if (x->d_idx) HIPCHK(hipFree(x->d_idx));
-    if (x->d_pos) HIPCHK(hipFree(x->d_pos));
-    x->d_idx = x->d_pos = nullptr;
-  }
-  x->n = n;
-  x->h_idx = idx;
-  x->h_pos = pos;
-  if (n > 0 && !ctx->host_only) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMalloc(&x->d_idx, n * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(x->d_idx, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&x->d_pos, n * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(x->d_pos, pos.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  return MPAS_DYC_OK;
+  XList& x = list_entry(*bp, location, halo_layer, direction, peer_rank, -1);
+  x.n = n;
+  x.h_idx = idx;
+  x.h_pos = pos;
+  CHK(upload_list(ctx, x.d_idx, x.h_idx));
+  return upload_list(ctx, x.d_pos, x.h_pos);
 }
 
 int mpas_dyc_comm_unique_id(void* id, int64_t nbytes) {
