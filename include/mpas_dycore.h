@@ -432,6 +432,12 @@ int32_t mpas_dyc_rccl_version(void);
  * nVertLevels > MPAS_DYC_MAX_LEVELS_WIDE: one workgroup per column in every kernel, of 256 lanes, 3
  * 512, 4 192, 5 320, 6 384, 7 448 lanes). */
 int mpas_dyc_block_layout(mpas_dyc_ctx* ctx, int32_t block, int32_t* out /* [4] */);
+/* Which Runge-Kutta stages of a step run their first acoustic cell phase in the launch of the
+ * tendencies' last cell kernel (k_dyn_cells3_acoustic_r): bit 0 = stage 1, bit 1 = stage 2, bit 2 =
+ * stage 3; 0 = none (several blocks or ranks, LBCs, more than 63 levels, a kernel family without
+ * the per-cell records, or MPAS_DYCORE_FUSE_TEND_ACOUSTIC=0).  A first stage of several sub-steps
+ * (order 2 with four or more) keeps the two kernels.  Valid once the mesh is set. */
+int mpas_dyc_fused_tend_acoustic(mpas_dyc_ctx* ctx);
 
 #ifdef __cplusplus
 }

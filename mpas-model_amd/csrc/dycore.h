@@ -80,7 +80,7 @@ struct Ptrs {
   double *rw, *rw_p, *rw_save, *wwAvg, *wwAvg_split;
   // what the acoustic cell phase reads for rw, w (tl2) and rho_zz (tl2): the fields themselves,
   // except in a dynamics substep's first stage (srk3 stage_fin), whose recovery writes the fields
-  const double *rw_rd, *w2_rd, *rho_zz2_rd;
+  const double *rw_rd, *w2_rd, *rho_zz2_rd, *ru_rd, *theta_m2_rd;
   double *ru, *ruAvg, *ruAvg_split, *ru_p, *ru_save, *cqu, *rho_edge, *v, *pv_edge, *gradPVn, *gradPVt;
   double *vorticity, *pv_vertex;
   double *uReconstructX, *uReconstructY, *uReconstructZ, *uReconstructZonal, *uReconstructMeridional;

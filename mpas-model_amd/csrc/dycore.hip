@@ -228,6 +228,9 @@ struct mpas_dyc_ctx {
   bool late_issue = false;
   // MPAS_DYCORE_OVERLAP_ALL=1: split the 642 and 876-887 exchanges even with nothing to overlap (A/B)
   bool overlap_all = false;
+  // dyn_tend's last cell kernel and the stage's first acoustic cell phase in one launch
+  // (k_dyn_cells3_acoustic_r, tend_acoustic_fused); MPAS_DYCORE_FUSE_TEND_ACOUSTIC=0: the two kernels
+  bool fuse_tend_acoustic = true;
   std::vector<XField> late_fs;
   bool late_pending = false;
   bool fused_pack_enabled = true;       // MPAS_DYCORE_FUSED_PACK=0: pack kernel instead (A/B)
@@ -569,6 +572,8 @@ Ptrs make_ptrs(mpas_dyc_ctx* c, Block& b) {
   p.rw_rd = p.rw;
   p.w2_rd = p.w2;
   p.rho_zz2_rd = p.rho_zz2;
+  p.ru_rd = p.ru;
+  p.theta_m2_rd = p.theta_m2;
   // 0-d mesh fields are mirrored on the host
   p.cf1 = b.fields[b.by_name["mesh.cf1"]].buf[1] ? *(double*)b.fields[b.by_name["mesh.cf1"]].buf[1] : 0.0;
   p.cf2 = b.fields[b.by_name["mesh.cf2"]].buf[1] ? *(double*)b.fields[b.by_name["mesh.cf2"]].buf[1] : 0.0;
@@ -843,6 +848,8 @@ Ptrs stage_pre(const Ptrs& p0, bool first_substep) {
   p.rw_rd = p.rw_save;
   p.rtheta_p = p.rtheta_p_save;
   p.theta_m2 = p.theta_m1;
+  p.ru_rd = p.ru_save;
+  p.theta_m2_rd = p.theta_m1;
   if (first_substep) {
     p.u2 = p.u1;
     p.w2 = p.w1;
@@ -854,10 +861,13 @@ Ptrs stage_pre(const Ptrs& p0, bool first_substep) {
 }
 
 // The first stage's last cell phase reads as stage_pre (rw_rd, w2_rd, rho_zz2_rd) but its fused
-// recovery (k_acoustic_cells_r<ME, true>) writes the fields themselves
+// recovery (k_acoustic_cells_r<ME, true>) writes the fields themselves; ru_rd and theta_m2_rd are
+// for the tendencies that k_dyn_cells3_acoustic_r computes in the same launch
 Ptrs stage_fin(const Ptrs& p0, bool first_substep) {
   Ptrs p = p0;
   p.rw_rd = p.rw_save;
+  p.ru_rd = p.ru_save;
+  p.theta_m2_rd = p.theta_m1;
   if (first_substep) {
     p.w2_rd = p.w1;
     p.rho_zz2_rd = p.rho_zz1;
@@ -929,13 +939,47 @@ void vert_imp_coefs(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dts)
   }
 }
 
+// The record kernels fuse the owned cells' recover_cells1 into a stage's last sub-step
+bool fused_recover(const Dims& d) { return batched(d) && (d.maxEdges == 6 || d.maxEdges == 7); }
+
+// A stage's first acoustic cell phase as dyn_tend launches it with its last cell kernel
+// (k_dyn_cells3_acoustic_r): the cell phase's pointers (stage_fin at rk 1) and arguments
+struct TendAcoustic {
+  Ptrs pf;
+  bool fin;  // the stage has one sub-step: the cell phase also recovers the owned cells
+  double dts, rdt, invNs;
+  int keep_pp, dl, store_tend;
+};
+// Whether stage rk_step of nsub sub-steps runs that launch: nothing lies between the two kernels
+// (no exchange, so no cell with a halo edge is left to k_smlstep_pert_b; no LBC kernels), both are
+// record kernels, one wavefront per column.  A first stage of several sub-steps (order 2 with four
+// or more) keeps the two kernels: its first cell phase would read through stage_pre, not stage_fin.
+bool tend_acoustic_fused(const mpas_dyc_ctx* ctx, int rk_step, int nsub) {
+#ifdef MPAS_WIDE
+  return false;
+#else
+  if (!ctx->fuse_tend_acoustic || needs_exchange(ctx) || ctx->lbc || ctx->blk.size() != 1) return false;
+  const Dims& d = ctx->blk[0].d;
+  return fuse_smlstep(d) && fused_recover(d) && !(rk_step == 1 && nsub > 1);
+#endif
+}
+// the sub-steps of each stage (atm_srk3, 296-322)
+void stage_sub_steps(const Config& cf, int n[3]) {
+  const int nss = cf.number_of_sub_steps;
+  n[0] = cf.time_integration_order == 3 ? 1 : std::max(1, nss / 2);
+  n[1] = std::max(1, nss / 2);
+  n[2] = nss;
+}
+
 // part: 0 = all kernels; 1 = only k_dyn_cells1, which reads nothing the exchange after the
 // diagnostics (1234-1249) or at the substep boundary (1282-1297) delivers; 2 = the rest
 // hdiv_done: the previous stage's w recovery computed h_divergence (recover_cells3 with hdiv), so
 // at rk_step 2 / 3, where k_dyn_cells1 computes nothing else, it is not launched
 // tp: the block's pack map of the tend_u exchange that follows (642, XPlan::fused_rec), or none
+// ta: the stage's first acoustic cell phase, to run in the launch of the last cell kernel
+// (k_dyn_cells3_acoustic_r), or nullptr
 void dyn_tend(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, int rk_step, double dt, int part = 0,
-              bool hdiv_done = false, bool last = true, XPack tp = XPack{}) {
+              bool hdiv_done = false, bool last = true, XPack tp = XPack{}, const TendAcoustic* ta = nullptr) {
   const Config& cf = ctx->cf;
   DynTendScal s{};
   s.rk_step = rk_step;
@@ -1015,6 +1059,23 @@ void dyn_tend(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, int rk_step, doub
   else if (pair_layout(d)) LAUNCH_PE((k_dyn_advflux_p<12, false>), (k_dyn_advflux_p<12, true>), d.nEdges, d, p);
   else if (d.maxEdges == 6) LAUNCH_E(k_dyn_advflux_b<10>, d.nEdges, d, p);
   else LAUNCH_E(k_dyn_advflux_b<12>, d.nEdges, d, p);
+#ifndef MPAS_WIDE
+  if (ta) {
+    // the launch takes the cell phase's pointers (stage_fin at rk 1): their ru_rd / rw_rd / w2_rd /
+    // rho_zz2_rd / theta_m2_rd are this stage's ru / rw / w2 / rho_zz2 / theta_m2, which the
+    // tendencies read
+    const TendAcArgs a{ta->dts, cf.epssm, ta->rdt, ta->invNs, rk_step, ta->keep_pp, ta->dl,
+                       ta->store_tend};
+    const bool m6 = d.maxEdges == 6, fin = ta->fin;
+    if (m6 && rk_step == 1) LAUNCH((k_dyn_cells3_acoustic_r<6, true, true>), d.nCells, d, ta->pf, cf, s, a);
+    if (m6 && rk_step != 1 && fin) LAUNCH((k_dyn_cells3_acoustic_r<6, false, true>), d.nCells, d, ta->pf, cf, s, a);
+    if (m6 && rk_step != 1 && !fin) LAUNCH((k_dyn_cells3_acoustic_r<6, false, false>), d.nCells, d, ta->pf, cf, s, a);
+    if (!m6 && rk_step == 1) LAUNCH((k_dyn_cells3_acoustic_r<7, true, true>), d.nCells, d, ta->pf, cf, s, a);
+    if (!m6 && rk_step != 1 && fin) LAUNCH((k_dyn_cells3_acoustic_r<7, false, true>), d.nCells, d, ta->pf, cf, s, a);
+    if (!m6 && rk_step != 1 && !fin) LAUNCH((k_dyn_cells3_acoustic_r<7, false, false>), d.nCells, d, ta->pf, cf, s, a);
+    return;
+  }
+#endif
   if (batched(d)) {
     const bool sml = fuse_smlstep(d);
     if (d.maxEdges == 6 && rk_step == 1 && sml) LAUNCH((k_dyn_cells3_r<6, true, true>), d.nCellsSolve, d, p, cf, s);
@@ -1078,9 +1139,6 @@ void acoustic_edges(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dts,
   else
     LAUNCH_E(k_acoustic_edges<false>, d.nEdges, d, p, dts, small_step, 0.0, phase, fresh);
 }
-
-// the record kernels fuse the owned cells' recover_cells1 into a stage's last sub-step
-bool fused_recover(const Dims& d) { return batched(d) && (d.maxEdges == 6 || d.maxEdges == 7); }
 
 // fin = 1: the stage's last sub-step, which also recovers the owned cells (k_acoustic_cells_r<ME,
 // true>) when fused_recover(d); rdt / invNs / rk_step are k_recover_cells1's arguments
@@ -1464,9 +1522,6 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
     rk_sub_timestep[0] = dt_dynamics / 3.;
     rk_sub_timestep[1] = dt_dynamics / (double)nss;
     rk_sub_timestep[2] = dt_dynamics / (double)nss;
-    number_sub_steps[0] = 1;
-    number_sub_steps[1] = std::max(1, nss / 2);
-    number_sub_steps[2] = nss;
   } else {
     rk_timestep[0] = dt_dynamics / 2.;
     rk_timestep[1] = dt_dynamics / 2.;
@@ -1474,10 +1529,8 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
     rk_sub_timestep[0] = dt_dynamics / (double)nss;
     rk_sub_timestep[1] = dt_dynamics / (double)nss;
     rk_sub_timestep[2] = dt_dynamics / (double)nss;
-    number_sub_steps[0] = std::max(1, nss / 2);
-    number_sub_steps[1] = std::max(1, nss / 2);
-    number_sub_steps[2] = nss;
   }
+  stage_sub_steps(cf, number_sub_steps);
   const bool scalars_in_dynamics = cf.scalar_advection && !cf.split_dynamics_transport;
   const bool split = split_phase(ctx);
   const bool lbc = ctx->lbc;  // config_apply_lbcs: regional boundary updates at the reference's points
@@ -1533,15 +1586,24 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
       const XPlan* xt = fused_rec_plan(ctx, xtu);
       auto tpk = [&](size_t ib) { return xt ? xt->rpk_edge[ib] : XPack{}; };
       auto tup = [&](size_t ib) { return xt ? xt->rup_edge[ib] : XUnpack{}; };
+      const double dts = rk_sub_timestep[rk_step - 1];
+      const int nsub = number_sub_steps[rk_step - 1];
+      // sub-step 1's cell phase in the launch of dyn_tend's last cell kernel (one block; tend_w and
+      // tend_theta are stored for a second sub-step or, after the dt's last stage, for the pool)
+      const bool fuse_ta = tend_acoustic_fused(ctx, rk_step, nsub);
+      TendAcoustic ta{};
+      if (fuse_ta)
+        ta = TendAcoustic{PF[0], nsub == 1, dts, rk_timestep[rk_step - 1], 1 / (double)nsub, last_stage ? 1 : 0,
+                          nsub == 1 ? damping_delta(ctx, ctx->blk[0].d, last_stage) : 0, (nsub > 1 || last_stage) ? 1 : 0};
+      const TendAcoustic* tap = fuse_ta ? &ta : nullptr;
       if (pending) {  // 561-630, k_dyn_cells1 overlapping the exchange
         EACHV(PS, dyn_tend(ctx, d, p, rk_step, dt, 1, hdiv_prev && batched(d)));
         CHK(xwait());
         pending = false;
-        EACHV(PS, dyn_tend(ctx, d, p, rk_step, dt, 2, false, last_stage, tpk(ib_)));
+        EACHV(PS, dyn_tend(ctx, d, p, rk_step, dt, 2, false, last_stage, tpk(ib_), tap));
       } else {
-        EACHV(PS, dyn_tend(ctx, d, p, rk_step, dt, 0, hdiv_prev && batched(d), last_stage, tpk(ib_)));  // 561-630
+        EACHV(PS, dyn_tend(ctx, d, p, rk_step, dt, 0, hdiv_prev && batched(d), last_stage, tpk(ib_), tap));  // 561-630
       }
-      const double dts = rk_sub_timestep[rk_step - 1];
       if (split && !sml_fused) {  // 642 | 644-678: interior cells overlap the tend_u exchange
         CHK(exchange_async(ctx, xtu));
         EACHV(PS, smlstep_pert(ctx, d, p, 1));
@@ -1579,7 +1641,6 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
       //   form that product themselves -- the cell phase of sub-step 1, then either the damped
       //   edge phase of sub-step 2 or, for a one-sub-step stage, the damping, which also stores
       //   ruAvg (on the same edges, so the 876 exchange and the recovery see the same values).
-      const int nsub = number_sub_steps[rk_step - 1];
       // (ru_p on layer 2 only, the reference's other "SMALLER STENCIL?" note at 877, changes owned values:
       // rejected)
       const unsigned rwp_layers = (!lbc && (ctx->halo_trim & 1)) ? 0x1u : ALL_LAYERS;
@@ -1629,7 +1690,8 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
         std::vector<XField> xf = {{"diag", "rtheta_pp", 0, 0x1u}};  // 845
         if (small_step < nsub) xf.push_back({"diag", "rho_pp", 0, 0x1u});  // 792 of the next sub-step
         const XPlan* xp = fused_pack_plan(ctx, xf);  // the cell phase packs this exchange's send buffer
-        EACHV(small_step == nsub ? PF : PS,
+        if (!(fuse_ta && small_step == 1))  // else: dyn_tend's last launch did this cell phase
+          EACHV(small_step == nsub ? PF : PS,
               acoustic_cells(ctx, d, p, dts, small_step, small_step == nsub, rk_timestep[rk_step - 1],
                             1 / (double)nsub, rk_step, needs_exchange(ctx) || last_stage,
                             xp ? xp->pack[ib_] : PackMap{}, damping_delta(ctx, d, last_stage),
@@ -2110,6 +2172,7 @@ int mpas_dyc_create_blocks(int32_t nblocks, const mpas_dyc_dims* dims, const mpa
   if (const char* pr = getenv("MPAS_DYCORE_P2P_RELEASE")) ctx->p2p_release = std::atoi(pr) != 0;
   if (const char* li = getenv("MPAS_DYCORE_LATE_ISSUE")) ctx->late_issue = std::string(li) == "1";
   if (const char* oa = getenv("MPAS_DYCORE_OVERLAP_ALL")) ctx->overlap_all = std::string(oa) == "1";
+  if (const char* ft = getenv("MPAS_DYCORE_FUSE_TEND_ACOUSTIC")) ctx->fuse_tend_acoustic = std::string(ft) != "0";
   if (const char* ov = getenv("MPAS_DYCORE_OVERLAP")) ctx->overlap = std::atoi(ov);
   for (auto& b : ctx->blk) {
     build_registry(b);
@@ -3226,6 +3289,17 @@ int mpas_dyc_block_layout(mpas_dyc_ctx* ctx, int32_t block, int32_t* out) {
   out[3] = 0;
 #endif
   return MPAS_DYC_OK;
+}
+
+int mpas_dyc_fused_tend_acoustic(mpas_dyc_ctx* ctx) {
+  if (!ctx || ctx->host_only) return 0;
+  if (hipSetDevice(ctx->device) != hipSuccess) return 0;
+  if (!ctx->bnd_ready && compute_bnd(ctx) != MPAS_DYC_OK) return 0;
+  int nsub[3], m = 0;
+  stage_sub_steps(ctx->cf, nsub);
+  for (int rk = 1; rk <= 3; ++rk)
+    if (tend_acoustic_fused(ctx, rk, nsub[rk - 1])) m |= 1 << (rk - 1);
+  return m;
 }
 
 double mpas_dyc_acoustic_bytes(const mpas_dyc_ctx* ctx) {

@@ -1383,10 +1383,26 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_advflux(Dims d, Ptrs p) {
 // k_dyn_cells3 on the per-cell stencil record (ME = maxEdges <= 7, RK1 = rk_step == 1): the
 // edge columns of every edge of the cell (and the cells across them) are loaded in one batch
 // after a single scalar round trip; the sums keep the reference order edge by edge.
-template <int ME, bool RK1, bool SML = false>
-__global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_r(Dims d, Ptrs p, Config cf, DynTendScal s) {
-  const int c = wave_elem(0);
-  if (c >= d.nCellsSolve) return;
+// The column's work is dyn_cells3_col, shared with k_dyn_cells3_acoustic_r (FUSE), which goes on
+// to the stage's first acoustic cell phase on the same cell with what TendCarry holds.
+// TendRd: the fields the recovery fused into that cell phase writes, as the tendencies read them
+// (in a dynamics substep's first stage the buffers stage_pre names).
+struct TendRd {
+  const double *ru, *rw, *w2, *rho_zz2, *theta_m2;
+};
+template <int ME>
+struct TendCarry {
+  double tw, tth;          // tend_w, tend_theta of the column
+  double ut[ME], thn[ME];  // tend_u of the cell's edges; rk > 1: theta_m (time level 1) of the cells across them
+  double sdv[ME];
+  double thc, zz, rz, rws, rw, w2, fzm, fzp, rdzw, invA;
+  int co[ME], ne;          // the cells across the edges
+};
+// FUSE: tend_u and zz are loaded for every cell (the cell phase reads them), and tend_w /
+// tend_theta are stored only with store_tend
+template <int ME, bool RK1, bool SML, bool FUSE>
+__device__ __forceinline__ void dyn_cells3_col(const Dims& d, const Ptrs& p, const Config& cf, const DynTendScal& s,
+                                               const TendRd& rd, int c, bool store_tend, TendCarry<ME>& cy) {
   const int k = lane_id(), K = d.K;
   const bool act = k < K;
   const bool actw = k <= K;
@@ -1401,7 +1417,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_r(Dims d, Ptrs p, 
 #pragma unroll
   for (int i = 0; i < ME; ++i) {
     const size_t oe = (size_t)st.e[i] * K + kc, oc = (size_t)st.o[i] * K + kc;
-    rue[i] = p.ru[oe];
+    rue[i] = rd.ru[oe];
     afw[i] = p.advflux_w[oe];
     aft[i] = p.advflux_th[oe];
     if (RK1) {
@@ -1423,18 +1439,18 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_r(Dims d, Ptrs p, 
   const double fzm = p.fzm[kc], fzp = p.fzp[kc], rdzu = p.rdzu[kc], rdzw_k = p.rdzw[kc];
   const double thc1 = p.theta_m1[o];
   const double twe0 = p.tend_w_euler[ow];
-  const double wk = p.w2[ow], rwk = p.rw[ow];
+  const double wk = rd.w2[ow], rwk = rd.rw[ow];
   const double ppk = p.pressure_p[o], dpk = p.dpdz[o], cqw = p.cqw[o];
-  const double rz = p.rho_zz2[o];
+  const double rz = rd.rho_zz2[o];
   const double dsw = del4w ? p.delsq_w[o] : 0.0, dst = del4t ? p.delsq_theta[o] : 0.0;
   const double tte0 = p.tend_theta_euler[o];
-  const double th = p.theta_m2[o], rws = p.rw_save[ow];
+  const double th = rd.theta_m2[o], rws = p.rw_save[ow];
   const double rtd = d.diabatic ? p.rt_diabatic_tend[o] : 0.0;
   // SML: the fused smlstep's tend_u of the cell's edges, issued with the rest (the zb column its
   // sign selects is loaded at the end: early, it would cost a wave per SIMD)
   const bool sml = SML && !(p.cell_bnd[c] & CELL_HALO_EDGE) && p.bdyMaskCell[c] <= N_RELAX_ZONE;
   double ut[ME], zz = 0.0;
-  if (sml) {
+  if (sml || FUSE) {
 #pragma unroll
     for (int i = 0; i < ME; ++i) ut[i] = p.tend_u[(size_t)uni(st.e[i]) * K + kc];
     zz = p.zz[o];
@@ -1552,7 +1568,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_r(Dims d, Ptrs p, 
     if (act && k >= 1) twf = (fzm * zz + fzp * zzm) * wt;
   }
   if (actw) {
-    p.tend_w[ow] = twf;
+    if (!FUSE || store_tend) p.tend_w[ow] = twf;
     if (RK1) p.tend_w_euler[ow] = twe;
   }
   if (act) {
@@ -1563,8 +1579,39 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_r(Dims d, Ptrs p, 
     }
     tt = tt + rz * rtd;
     if (RK1) p.tend_theta_euler[o] = tte;
-    p.tend_theta[o] = tt + tte + PHYS(p.tend_rtheta_physics, o);
+    tt = tt + tte + PHYS(p.tend_rtheta_physics, o);
+    if (!FUSE || store_tend) p.tend_theta[o] = tt;
   }
+  if (FUSE) {
+    cy.tw = twf;
+    cy.tth = tt;
+#pragma unroll
+    for (int i = 0; i < ME; ++i) {
+      cy.ut[i] = ut[i];
+      if (!RK1) cy.thn[i] = x2[i];
+      cy.sdv[i] = sdv[i];
+      cy.co[i] = st.o[i];
+    }
+    cy.thc = thc1;
+    cy.zz = zz;
+    cy.rz = rz;
+    cy.rws = rws;
+    cy.rw = rwk;
+    cy.w2 = wk;
+    cy.fzm = fzm;
+    cy.fzp = fzp;
+    cy.rdzw = rdzw_k;
+    cy.invA = invA;
+    cy.ne = st.ne;
+  }
+}
+
+template <int ME, bool RK1, bool SML = false>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_r(Dims d, Ptrs p, Config cf, DynTendScal s) {
+  const int c = wave_elem(0);
+  if (c >= d.nCellsSolve) return;
+  TendCarry<ME> cy;
+  dyn_cells3_col<ME, RK1, SML, false>(d, p, cf, s, TendRd{p.ru, p.rw, p.w2, p.rho_zz2, p.theta_m2}, c, true, cy);
 }
 
 // k_dyn_advflux with batched loads (NA = 2*maxEdges-2 >= nAdvCellsForEdge): the edge's index
@@ -3418,68 +3465,44 @@ __device__ __forceinline__ void pack_rec_cell(const XPack& pk, int c, int k, boo
   }
 }
 
-// rp: the stage's last sub-step (FIN) also packs the 876-887 exchange (XPack), or nothing
-// The 320-lane build (K = 256..319): a column's five wavefronts wait at the solve's barriers while
-// one of them sweeps, so the sub-step form runs at 5 wavefronts per SIMD (96 VGPRs, four columns
-// per CU instead of three): 6.43 -> 5.63 ms per sub-step, 0.9-2.6 ms per dt at 163842 x 300
-// (profiles/r06_ab_acoustic_cells_wide_occupancy_k300.log).  The FIN form keeps its 4 (at 96
-// VGPRs it spills 92-108 bytes per lane and ran slower); the other builds gain nothing measurable.
-#if defined(MPAS_WIDE) && WIDE_THREADS == 320
-#define ACOUSTIC_CELLS_ATTR __attribute__((amdgpu_waves_per_eu(FIN ? 4 : 5)))
-#else
-#define ACOUSTIC_CELLS_ATTR
-#endif
-template <int ME, bool FIN = false>
-__global__ __launch_bounds__(BLOCK_THREADS) ACOUSTIC_CELLS_ATTR void k_acoustic_cells_r(Dims d, Ptrs p, double dts, int small_step,
-                                                                    double epssm, double rdt = 0.0,
-                                                                    double invNs = 0.0, int rk_step = 0,
-                                                                    int keep_pp = 1, PackMap pk = PackMap{}, int dl = 0,
-                                                                    XPack rp = XPack{}) {
-  const int c = wave_elem(0);
-  if (c >= d.nCells) return;
+// The cell phase's operands in registers (AcIn) and its work on them (acoustic_cells_col), shared by
+// k_acoustic_cells_r, which loads them all, and k_dyn_cells3_acoustic_r, which has most of them
+// from the tendencies of the same column
+template <int ME>
+struct AcIn {
+  int ne;
+  double sdv[ME], invA, spec;
+  double rtpp, rhopp, rwp, wwa;
+  double thc, trho, tth, tw, ru[ME], th[ME];
+  double coftz, zz, cofwt, cofwz, cofwr, a_tri, alpha_tri, gamma_tri;
+  double rz, dss, rws, rw, w2, cofrz, rdzw, fzm, fzp;
+};
+// the operands that only the cell phase reads: tend_rho and the coefficients of atm_compute_vert_imp_coefs
+template <int ME>
+__device__ __forceinline__ void load_ac_own(const Ptrs& p, size_t o, size_t ow, int kc, AcIn<ME>& in) {
+  in.trho = p.tend_rho[o];
+  in.coftz = p.coftz[ow], in.cofwt = p.cofwt[o], in.cofwz = p.cofwz[o], in.cofwr = p.cofwr[o];
+  in.a_tri = p.a_tri[o], in.alpha_tri = p.alpha_tri[o], in.gamma_tri = p.gamma_tri[o];
+  in.dss = p.dss[o];
+  in.cofrz = p.cofrz[kc];
+}
+template <int ME, bool FIN>
+__device__ __forceinline__ void acoustic_cells_col(const Dims& d, const Ptrs& p, int c, const AcIn<ME>& in, double dts,
+                                                   int small_step, double epssm, double rdt, double invNs, int rk_step,
+                                                   int keep_pp, const PackMap& pk, int dl, const XPack& rp) {
   const int k = lane_id(), K = d.K;
   const bool act = k < K, actw = k <= K;
-  const int kc = min(k, K - 1), kw = min(k, K);  // clamped lanes load in bounds and store nothing
+  const int kc = min(k, K - 1), kw = min(k, K);
   const size_t K1 = K + 1;
   const size_t o = (size_t)c * K + kc, ow = (size_t)c * K1 + kw;
-  // sub-step 1 starts from zero perturbations (2617-2622): rtheta_pp, rho_pp, rw_p and wwAvg are
-  // not read then (the values would be replaced by 0 below), which saves four streams
-  const bool first = small_step == 1;
-  double rtpp = first ? 0.0 : p.rtheta_pp[o];
-  if (c >= d.nCellsSolve) {
-    if (act) p.rtheta_pp_old[o] = (FIN && dl) ? rtpp - (first ? 0.0 : rtpp) : (first ? 0.0 : rtpp);
-    return;
-  }
-  int re[ME], rc[ME];
-  double sdv[ME];
-#pragma unroll
-  for (int i = 0; i < ME; ++i) {
-    re[i] = p.cell_rec[(size_t)c * CELL_REC + i];
-    rc[i] = p.cell_rec[(size_t)c * CELL_REC + CELL_REC_ME + i];
-    sdv[i] = ld_uniform_f64(p.cell_sdv + (size_t)c * ME + i);
-  }
-  const int ne = p.cell_rec[(size_t)c * CELL_REC + 14];
-  const double invA = p.invAreaCell[c], spec = p.specZoneMaskCell[c];
-  double rhopp = first ? 0.0 : p.rho_pp[o], rwp = first ? 0.0 : p.rw_p[ow], wwa = first ? 0.0 : p.wwAvg[ow];
-  const double thc = p.theta_m1[o], trho = p.tend_rho[o], tth = p.tend_theta[o], tw = p.tend_w[ow];
-  double ru[ME], th[ME];
-  // sub-step 1: ru_p = dts * tend_u (794-837), formed here; srk3 launches no edge phase for it
-  const double* __restrict__ rusrc = small_step == 1 ? p.tend_u : p.ru_p;
-#pragma unroll
-  for (int i = 0; i < ME; ++i) {
-    ru[i] = rusrc[(size_t)re[i] * K + kc];
-    th[i] = p.theta_m1[(size_t)rc[i] * K + kc];
-  }
-  if (small_step == 1) {
-#pragma unroll
-    for (int i = 0; i < ME; ++i) ru[i] = dts * ru[i];
-  }
-  const double coftz = p.coftz[ow], zz = p.zz[o], cofwt = p.cofwt[o], cofwz = p.cofwz[o], cofwr = p.cofwr[o];
-  const double a_tri = p.a_tri[o], alpha_tri = p.alpha_tri[o], gamma_tri = p.gamma_tri[o];
-  // rho_zz (tl2), rw and w (tl2) through the *_rd pointers: in a dynamics substep's first stage
-  // they name the buffers that hold these values until the recovery (srk3, stage_fin)
-  const double rz = p.rho_zz2_rd[o], dss = p.dss[o], rws = p.rw_save[ow], rw = p.rw_rd[ow], w2 = p.w2_rd[ow];
-  const double cofrz = p.cofrz[kc], rdzw = p.rdzw[kc], fzm = p.fzm[kc], fzp = p.fzp[kc];
+  const int ne = in.ne;
+  const double invA = in.invA, spec = in.spec;
+  double rtpp = in.rtpp, rhopp = in.rhopp, rwp = in.rwp, wwa = in.wwa;
+  const double thc = in.thc, trho = in.trho, tth = in.tth, tw = in.tw;
+  const double coftz = in.coftz, zz = in.zz, cofwt = in.cofwt, cofwz = in.cofwz, cofwr = in.cofwr;
+  const double a_tri = in.a_tri, alpha_tri = in.alpha_tri, gamma_tri = in.gamma_tri;
+  const double rz = in.rz, dss = in.dss, rws = in.rws, rw = in.rw, w2 = in.w2;
+  const double cofrz = in.cofrz, rdzw = in.rdzw, fzm = in.fzm, fzp = in.fzp;
   RecIn ri{};
   const double rtpp_old = (small_step == 1) ? 0.0 : rtpp;
   const double resm = (1.0 - epssm) / (1.0 + epssm);
@@ -3490,9 +3513,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) ACOUSTIC_CELLS_ATTR void k_acoustic_
 #pragma unroll
     for (int i = 0; i < ME; ++i) {
       if (i < ne) {
-        const double flux = dts * sdv[i] * ru[i] * invA;  // == sign * dts * dvEdge * ru_p * invAreaCell
+        const double flux = dts * in.sdv[i] * in.ru[i] * invA;  // == sign * dts * dvEdge * ru_p * invAreaCell
         rs = rs - flux;
-        ts = ts - flux * 0.5 * (th[i] + thc);  // (th2 + th1): the sum commutes exactly
+        ts = ts - flux * 0.5 * (in.th[i] + thc);  // (th2 + th1): the sum commutes exactly
       }
     }
     double dn2[2] = {coftz, rwp};  // levels k+1 (one LDS round trip in the wide build)
@@ -3572,6 +3595,136 @@ __global__ __launch_bounds__(BLOCK_THREADS) ACOUSTIC_CELLS_ATTR void k_acoustic_
     if (FIN) recover_cell_fused(d, p, c, k, zz, rws, fzm, fzp, ri, rhopp, rtpp, rwp, wwa, rdt, invNs, rk_step);
   }
 }
+
+// rp: the stage's last sub-step (FIN) also packs the 876-887 exchange (XPack), or nothing
+// The 320-lane build (K = 256..319): a column's five wavefronts wait at the solve's barriers while
+// one of them sweeps, so the sub-step form runs at 5 wavefronts per SIMD (96 VGPRs, four columns
+// per CU instead of three): 6.43 -> 5.63 ms per sub-step, 0.9-2.6 ms per dt at 163842 x 300
+// (profiles/r06_ab_acoustic_cells_wide_occupancy_k300.log).  The FIN form keeps its 4 (at 96
+// VGPRs it spills 92-108 bytes per lane and ran slower); the other builds gain nothing measurable.
+#if defined(MPAS_WIDE) && WIDE_THREADS == 320
+#define ACOUSTIC_CELLS_ATTR __attribute__((amdgpu_waves_per_eu(FIN ? 4 : 5)))
+#else
+#define ACOUSTIC_CELLS_ATTR
+#endif
+template <int ME, bool FIN = false>
+__global__ __launch_bounds__(BLOCK_THREADS) ACOUSTIC_CELLS_ATTR void k_acoustic_cells_r(Dims d, Ptrs p, double dts, int small_step,
+                                                                    double epssm, double rdt = 0.0,
+                                                                    double invNs = 0.0, int rk_step = 0,
+                                                                    int keep_pp = 1, PackMap pk = PackMap{}, int dl = 0,
+                                                                    XPack rp = XPack{}) {
+  const int c = wave_elem(0);
+  if (c >= d.nCells) return;
+  const int k = lane_id(), K = d.K;
+  const bool act = k < K, actw = k <= K;
+  const int kc = min(k, K - 1), kw = min(k, K);  // clamped lanes load in bounds and store nothing
+  const size_t K1 = K + 1;
+  const size_t o = (size_t)c * K + kc, ow = (size_t)c * K1 + kw;
+  // sub-step 1 starts from zero perturbations (2617-2622): rtheta_pp, rho_pp, rw_p and wwAvg are
+  // not read then (the values would be replaced by 0 below), which saves four streams
+  const bool first = small_step == 1;
+  double rtpp = first ? 0.0 : p.rtheta_pp[o];
+  if (c >= d.nCellsSolve) {
+    if (act) p.rtheta_pp_old[o] = (FIN && dl) ? rtpp - (first ? 0.0 : rtpp) : (first ? 0.0 : rtpp);
+    return;
+  }
+  AcIn<ME> in;
+  int re[ME], rc[ME];
+#pragma unroll
+  for (int i = 0; i < ME; ++i) {
+    re[i] = p.cell_rec[(size_t)c * CELL_REC + i];
+    rc[i] = p.cell_rec[(size_t)c * CELL_REC + CELL_REC_ME + i];
+    in.sdv[i] = ld_uniform_f64(p.cell_sdv + (size_t)c * ME + i);
+  }
+  in.ne = p.cell_rec[(size_t)c * CELL_REC + 14];
+  // the sub-step form reads the cell's two scalars on the scalar unit (96 VGPRs, 5 waves per SIMD);
+  // the FIN form has no SGPRs to spare for them
+  in.invA = FIN ? p.invAreaCell[c] : ld_uniform_f64(p.invAreaCell + c);
+  in.spec = FIN ? p.specZoneMaskCell[c] : ld_uniform_f64(p.specZoneMaskCell + c);
+  in.rtpp = rtpp;
+  in.rhopp = first ? 0.0 : p.rho_pp[o], in.rwp = first ? 0.0 : p.rw_p[ow], in.wwa = first ? 0.0 : p.wwAvg[ow];
+  in.thc = p.theta_m1[o], in.trho = p.tend_rho[o], in.tth = p.tend_theta[o], in.tw = p.tend_w[ow];
+  // sub-step 1: ru_p = dts * tend_u (794-837), formed here; srk3 launches no edge phase for it
+  const double* __restrict__ rusrc = small_step == 1 ? p.tend_u : p.ru_p;
+#pragma unroll
+  for (int i = 0; i < ME; ++i) {
+    in.ru[i] = rusrc[(size_t)re[i] * K + kc];
+    in.th[i] = p.theta_m1[(size_t)rc[i] * K + kc];
+  }
+  if (small_step == 1) {
+#pragma unroll
+    for (int i = 0; i < ME; ++i) in.ru[i] = dts * in.ru[i];
+  }
+  in.coftz = p.coftz[ow], in.zz = p.zz[o], in.cofwt = p.cofwt[o], in.cofwz = p.cofwz[o], in.cofwr = p.cofwr[o];
+  in.a_tri = p.a_tri[o], in.alpha_tri = p.alpha_tri[o], in.gamma_tri = p.gamma_tri[o];
+  // rho_zz (tl2), rw and w (tl2) through the *_rd pointers: in a dynamics substep's first stage
+  // they name the buffers that hold these values until the recovery (srk3, stage_fin)
+  in.rz = p.rho_zz2_rd[o], in.dss = p.dss[o], in.rws = p.rw_save[ow], in.rw = p.rw_rd[ow], in.w2 = p.w2_rd[ow];
+  in.cofrz = p.cofrz[kc], in.rdzw = p.rdzw[kc], in.fzm = p.fzm[kc], in.fzp = p.fzp[kc];
+  acoustic_cells_col<ME, FIN>(d, p, c, in, dts, small_step, epssm, rdt, invNs, rk_step, keep_pp, pk, dl, rp);
+}
+
+#ifndef MPAS_WIDE
+// dyn_tend's last cell kernel (k_dyn_cells3_r<ME, RK1, true>) and the stage's first acoustic cell
+// phase (k_acoustic_cells_r<ME, FIN> at small_step 1) on the same owned cell, in one launch: srk3
+// runs them back to back when the block has no halo (no exchange, no cell left to
+// k_smlstep_pert_b) and no LBCs.  The cell phase takes tend_w, tend_theta, the tend_u of the
+// cell's edges, theta_m across them and the column's own theta_m, zz, rho_zz, rw_save, rw and w
+// from the tendencies' registers (TendCarry) instead of loading them again; both parts are the
+// device functions the two kernels call, so the bits are theirs.
+// The fused recovery writes only own-column fields of cell c (rho_zz, rw, w, theta_m of time
+// level 2, rtheta_p, wwAvg, exner, pressure_p, rho_p) and the tendencies read those of cell c
+// only; what they read of other cells (theta_m of time level 1, delsq_*, the edge fields) is not
+// written here.
+// a.store_tend = 0: tend_w and tend_theta are not stored (the stage has no second sub-step to read
+// them and is not the dt's last, whose values the pool keeps)
+struct TendAcArgs {
+  double dts, epssm, rdt, invNs;
+  int rk_step, keep_pp, dl, store_tend;
+};
+template <int ME, bool RK1, bool FIN>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_acoustic_r(Dims d, Ptrs p, Config cf, DynTendScal s,
+                                                                         TendAcArgs a) {
+  const int c = wave_elem(0);
+  if (c >= d.nCells) return;
+  const int k = lane_id(), K = d.K;
+  const int kc = min(k, K - 1), kw = min(k, K);
+  const size_t o = (size_t)c * K + kc, ow = (size_t)c * (K + 1) + kw;
+  if (c >= d.nCellsSolve) {  // a halo cell's share of the cell phase at sub-step 1
+    if (k < K) p.rtheta_pp_old[o] = 0.0;
+    return;
+  }
+  TendCarry<ME> cy;
+  dyn_cells3_col<ME, RK1, true, true>(d, p, cf, s, TendRd{p.ru_rd, p.rw_rd, p.w2_rd, p.rho_zz2_rd, p.theta_m2_rd}, c,
+                                      a.store_tend != 0, cy);
+  AcIn<ME> in;
+  // the cell phase's own operands after the tendencies' gathers have been consumed: with them they
+  // would be live across the whole tendency part
+  load_ac_own(p, o, ow, kc, in);
+  // rk 1's tendencies do not read theta_m (time level 1) across the edges; gathered here and not
+  // with the tendencies' loads, the rk 1 form (ME = 6) needs 157 VGPRs instead of 169: 3 waves per
+  // SIMD instead of 2 (at 2 it ran slower than the two kernels)
+  if (RK1) {
+#pragma unroll
+    for (int i = 0; i < ME; ++i) cy.thn[i] = p.theta_m1[(size_t)cy.co[i] * K + kc];
+  }
+  in.spec = ld_uniform_f64(p.specZoneMaskCell + c);
+  in.ne = cy.ne;
+  in.invA = cy.invA;
+  in.rtpp = in.rhopp = in.rwp = in.wwa = 0.0;  // sub-step 1 starts from zero perturbations
+  in.thc = cy.thc, in.tth = cy.tth, in.tw = cy.tw;
+#pragma unroll
+  for (int i = 0; i < ME; ++i) {
+    in.sdv[i] = cy.sdv[i];
+    in.ru[i] = a.dts * cy.ut[i];  // ru_p = dts * tend_u (794-837)
+    in.th[i] = cy.thn[i];
+  }
+  in.zz = cy.zz, in.rz = cy.rz, in.rws = cy.rws, in.rw = cy.rw, in.w2 = cy.w2;
+  in.rdzw = cy.rdzw, in.fzm = cy.fzm, in.fzp = cy.fzp;
+  acoustic_cells_col<ME, FIN>(d, p, c, in, a.dts, 1, a.epssm, a.rdt, a.invNs, a.rk_step, a.keep_pp, PackMap{}, a.dl,
+                              XPack{});
+}
+#endif
 
 // cell phase (2603-2721): rtheta_pp_old for all cells, column solve for owned cells
 __global__ __launch_bounds__(BLOCK_THREADS) void k_acoustic_cells(Dims d, Ptrs p, double dts, int small_step, double epssm) {

@@ -464,6 +464,13 @@ class Dycore:
                 "column": ("wavefront", "wide", "wide256", "wide512", "wide192", "wide320", "wide384",
                            "wide448")[out[3]]}
 
+    def fused_tend_acoustic(self) -> tuple:
+        """The Runge-Kutta stages (1..3) whose first acoustic cell phase runs in the launch of the
+        tendencies' last cell kernel (mpas_dyc_fused_tend_acoustic); () when none does: several
+        blocks or ranks, LBCs, more than 63 levels, or MPAS_DYCORE_FUSE_TEND_ACOUSTIC=0."""
+        m = int(self.lib.mpas_dyc_fused_tend_acoustic(self.h))
+        return tuple(rk for rk in (1, 2, 3) if m & (1 << (rk - 1)))
+
     def exchange_profile(self, dt: float, itimestep: int = 1) -> dict:
         """One eager atm_timestep with HIP events around every exchange's exposed part and every
         RCCL group (mpas_dyc_set_profile / mpas_dyc_get_profile); synchronous.  Shift the time

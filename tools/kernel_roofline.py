@@ -35,7 +35,8 @@ DYCORE = os.path.join(os.path.dirname(HERE), "mpas-model_amd", "csrc", "dycore.h
 ALIAS = {"u1": "state.u", "u2": "state.u", "w1": "state.w", "w2": "state.w", "w2_rd": "state.w",
          "theta_m1": "state.theta_m", "theta_m2": "state.theta_m", "rho_zz1": "state.rho_zz",
          "rho_zz2": "state.rho_zz", "rho_zz2_rd": "state.rho_zz", "scalars1": "state.scalars",
-         "scalars2": "state.scalars", "rw_rd": "diag.rw", "tend_u": "tend.u", "tend_u_euler": "tend.u_euler",
+         "scalars2": "state.scalars", "rw_rd": "diag.rw", "ru_rd": "diag.ru", "theta_m2_rd": "state.theta_m",
+         "tend_u": "tend.u", "tend_u_euler": "tend.u_euler",
          "tend_w": "tend.w", "tend_w_euler": "tend.w_euler", "tend_theta": "tend.theta_m",
          "tend_theta_euler": "tend.theta_euler", "tend_rho": "tend.rho_zz", "rt_diabatic_tend": "tend.rt_diabatic_tend",
          "scalars_tend": "tend.scalars_tend"}
@@ -63,6 +64,22 @@ VARIANT = {
                                     "drop_w": {"exner", "pressure_p", "rho_p", "rho_zz2", "rtheta_p", "rw", "theta_m2",
                                                "w2"}},
     "k_acoustic_cells_r<6, true": {"drop_w": {"rho_pp", "rw_p", "rtheta_pp"}},
+    # the tendencies and sub-step 1's cell phase in one launch: the rules of the two kernels above;
+    # tend_w / tend_theta are stored for a second sub-step only (the dt's last stage aside)
+    "k_dyn_cells3_acoustic_r<6, true, true": {"drop": {"ru_save", "tend_rtheta_physics"},
+                                              "drop_w": {"rthdynten", "tend_rtheta_adv", "tend_w", "tend_theta",
+                                                         "rho_pp", "rw_p", "rtheta_pp"}},
+    "k_dyn_cells3_acoustic_r<6, false, true": {"drop": {"delsq_theta", "delsq_w", "dpdz", "pressure_p", "t_init", "zgrid",
+                                                        "cqw", "meshScalingDel4", "rdzu", "tend_rtheta_physics"},
+                                               "drop_w": {"tend_theta_euler", "tend_w_euler", "rthdynten", "tend_rtheta_adv",
+                                                          "tend_w", "tend_theta", "rho_pp", "rw_p", "rtheta_pp"}},
+    "k_dyn_cells3_acoustic_r<6, false, false": {"drop": {"delsq_theta", "delsq_w", "dpdz", "pressure_p", "t_init", "zgrid",
+                                                         "cqw", "meshScalingDel4", "rdzu", "tend_rtheta_physics",
+                                                         "rho_base", "rho_p_save", "rtheta_base", "rtheta_p_save",
+                                                         "exner_base"},
+                                                "drop_w": {"tend_theta_euler", "tend_w_euler", "rthdynten", "tend_rtheta_adv",
+                                                           "exner", "pressure_p", "rho_p", "rho_zz2", "rtheta_p", "rw",
+                                                           "theta_m2", "w2"}},
     "k_divdamp_p<true": {},
     "k_acoustic_edges_p<true": {},
     "k_diag_edges_p": {"drop_w": {"gradPVn", "gradPVt"}},
