@@ -91,7 +91,8 @@ void mpas_dyc_destroy(mpas_dyc_ctx* ctx);
 const char* mpas_dyc_last_error(const mpas_dyc_ctx* ctx);
 
 /* Host <-> device copy of one named pool field (pool: "mesh","state","diag","tend",
- * "tend_physics"; scalars 0-d fields cf1/cf2/cf3 take 8 bytes). nbytes must match. */
+ * "tend_physics", "lbc", "tend_iau" -- see mpas_dyc_set_iau; scalars 0-d fields cf1/cf2/cf3 take 8
+ * bytes). nbytes must match. */
 int mpas_dyc_set_field(mpas_dyc_ctx* ctx, const char* pool, const char* name, int32_t time_level,
                        const void* host, int64_t nbytes);
 int mpas_dyc_get_field(mpas_dyc_ctx* ctx, const char* pool, const char* name, int32_t time_level,
@@ -122,7 +123,9 @@ int mpas_dyc_init_diagnostics(mpas_dyc_ctx* ctx, double dt);
  * atm_compute_solve_diagnostics (with the init exchanges), on a state whose coupled fields
  * (theta_m, rho_zz, rho_p, rtheta_p, exner, pressure_p, ru, rw, ...) the host has set. */
 int mpas_dyc_solve_diagnostics(mpas_dyc_ctx* ctx, double dt);
-/* atm_timestep -> atm_srk3: advance time level 1 to time level 2 by dt. Asynchronous. */
+/* atm_timestep -> atm_srk3: advance time level 1 to time level 2 by dt. Asynchronous.  itimestep is
+ * the model's step counter (1 = the first step of the run): with mpas_dyc_set_iau on it decides whether
+ * the step is inside the IAU window; nothing else reads it. */
 int mpas_dyc_timestep(mpas_dyc_ctx* ctx, double dt, int32_t itimestep);
 /* mpas_pool_shift_time_levels(state): swap time levels 1 and 2 (pointer swap).  Between steps, only
  * time level 1 (the state the last step produced) is defined for u and w: the step does not copy
@@ -152,6 +155,42 @@ int mpas_dyc_synchronize(mpas_dyc_ctx* ctx);
  * mpas_dyc_timestep runs them itself and mpas_dyc_finish_step does nothing. */
 #define MPAS_DYC_PHYSICS_MICROPHYSICS 4
 int mpas_dyc_set_physics(mpas_dyc_ctx* ctx, int32_t flags);
+/* Incremental analysis update: the branch of atm_srk3 after physics_get_tend
+ * (mpas_atm_time_integration.F:459-469 -> atm_add_tend_anal_incr, mpas_atm_iau.F:81-217).  The host sets
+ * the analysis-minus-background increments of the reference's tend_iau pool (Registry.xml:3101-3132,
+ * the `iau` input stream) with mpas_dyc_set_field(ctx, "tend_iau", name, ...):
+ *   tend_iau.u (K, nEdges+1), tend_iau.theta and tend_iau.rho (K, nCells+1),
+ *   tend_iau.scalars (ns, K, nCells+1; scalar-major in HBM like state.scalars);
+ * the pool is allocated at its first set_field or at mpas_dyc_set_iau(on), and is zero until set.  With
+ * IAU on, every mpas_dyc_timestep whose itimestep <= nint(window_length_s / dt) adds, on the owned
+ * edges and cells and with wgt = 1 / window_length_s, in the Fortran's operand order,
+ *   tend_ru_physics     += wgt rho_edge u_amb                                             (:170)
+ *   tend_rho_physics    += wgt rho_amb / zz                                               (:177)
+ *   scalars_tend(moist) += wgt (scalars_amb rho_zz + scalars rho_amb / zz)                (:198-199)
+ *   tend_rtheta_physics += (1 + Rv/Rd qv) wgt (theta_amb rho_zz + theta rho_amb / zz)
+ *                          + Rv/Rd theta scalars_tend(qv),   theta = theta_m / (1 + Rv/Rd qv)  (:190-209)
+ * from rho_edge of the previous solve_diagnostics and theta_m, rho_zz, scalars of time level 1; no w
+ * forcing (:145).  The sums go into arrays of the library's own, which the step reads in place of
+ * tend_physics.*: what the host set there stays as it set it (the reference refills its module scratch
+ * every step; here a host may set the arrays once).  tend.scalars_tend is updated in place, as in the
+ * reference: the host sets it before every step when it supplies physics tendencies.
+ * IAU on implies the step of MPAS_DYC_PHYSICS_TENDENCIES for as long as it is on, after the window
+ * too -- scalars_tend feeds the scalar transport instead of being zeroed there (3437, 3743), and
+ * negative scalars of time level 2 are set to zero at the end of the step (1645-1646) -- because the
+ * reference without DO_PHYSICS would drop the moisture increments.  A host that has not set that flag
+ * itself gets what it would have supplied: tend_*_physics of 0.0, and a scalars_tend that is 0.0 before
+ * the IAU term of every step.  MPAS_DYC_PHYSICS_RQVDYNTEN and _MICROPHYSICS are not implied.
+ * on = config_IAU_option ('off' = 0, 'on' = 1); window_length_s = config_IAU_window_length_s
+ * (Registry.xml:355-362), <= 0 with on = 1: MPAS_DYC_EINVAL.  A captured step (mpas_dyc_use_graph) is
+ * kept per branch -- forced, with the two IAU kernels, and unforced, without them -- so a run past its
+ * window pays nothing and no step is captured again because itimestep changed; changing the switch
+ * or the window drops the captured steps.  Works on MPAS_DYC_HOST_ONLY contexts (for
+ * mpas_dyc_iau_weight; the field calls there return MPAS_DYC_ESTATE as always). */
+int mpas_dyc_set_iau(mpas_dyc_ctx* ctx, int32_t on, double window_length_s);
+/* atm_iau_coef (mpas_atm_iau.F:22-78) of step itimestep: *wgt = 1 / window_length_s if itimestep <=
+ * nint(window_length_s / dt) (halves round away from zero), else 0; 0 with IAU off.  A weight <= 1e-12
+ * leaves the step unforced (:118).  Works on MPAS_DYC_HOST_ONLY contexts. */
+int mpas_dyc_iau_weight(const mpas_dyc_ctx* ctx, double dt, int32_t itimestep, double* wgt);
 /* The end of atm_srk3 after the host's microphysics (see MPAS_DYC_PHYSICS_MICROPHYSICS); call it
  * before mpas_dyc_shift_time_levels.  Asynchronous. */
 int mpas_dyc_finish_step(mpas_dyc_ctx* ctx, double dt);
@@ -412,7 +451,9 @@ double mpas_dyc_acoustic_bytes(const mpas_dyc_ctx* ctx);
  * reaches the join until the exchange stream's work has completed -- and around each RCCL group.
  * mpas_dyc_get_profile then returns, for the last such step: out[0] = exchanges waited on,
  * out[1] = ms of the step (events on the compute stream), out[2] = ms of exposed exchange time,
- * out[3] = RCCL groups issued, out[4] = ms inside them (mostly overlapped with compute). */
+ * out[3] = RCCL groups issued, out[4] = ms inside them (mostly overlapped with compute).
+ * out[5] (profile on or off) = steps captured into a hipGraph since the context was created: it
+ * stays put while steps replay (one capture per buffer layout and IAU branch, mpas_dyc_set_iau). */
 int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on);
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n);
 /* The plan key of the exchange whose RCCL group was enqueued last ("warm_rccl <key>" while the

@@ -31,6 +31,7 @@
 #include "summary.hip"
 #include "lbc.hip"
 #include "model_init.hip"
+#include "iau.hip"
 
 using namespace mpas;
 
@@ -251,6 +252,14 @@ struct mpas_dyc_ctx {
   // default is config_print_global_minmax_vel = true, Registry.xml:339)
   int summary_flags = MPAS_DYC_PRINT_GLOBAL_MINMAX_VEL;
   int summary_tl = 0;                   // time level the records describe (0: none yet)
+  // incremental analysis update (mpas_dyc_set_iau; iau.hip): config_IAU_option / _window_length_s, and
+  // atm_iau_coef of the step being enqueued (> 1e-12: the step applies the forcing).  iau_stale: the
+  // library's own tendencies (scratch.iau_*, tend.scalars_tend of a host that supplies none) hold a
+  // forced step's sums and are zeroed before the next unforced one reads them
+  int iau_on = 0;
+  double iau_window = 0.0, iau_wgt = 0.0;
+  bool iau_stale = false;
+  int64_t graph_captures = 0;           // steps captured so far (mpas_dyc_get_profile out[5])
   bool tail_pending = false;            // MPAS_DYC_PHYSICS_MICROPHYSICS: a step ran, mpas_dyc_finish_step not yet
   // exchange profile (mpas_dyc_set_profile): eager steps with HIP events around the exposed part of
   // every exchange (a blocking exchange whole; a split-phase one from the compute stream reaching
@@ -472,6 +481,20 @@ void build_registry(Block& c) {
   for (const char* n : {"deriv_two", "zb", "zb3", "meshDensity", "areaCell", "areaTriangle", "xCell", "yCell", "zCell",
                         "xEdge", "yEdge", "zEdge", "meshDensity_root4", "meshDensityEdge_root4", "dss_sin"})
     c.fields[c.by_name[std::string("mesh.") + n]].lazy = true;
+  // the tend_iau pool (Registry.xml:3101-3132): the analysis increments of the incremental analysis
+  // update, and the step's physics + IAU tendencies (iau.hip); allocated, zeroed, at the first
+  // set_field of the pool or at mpas_dyc_set_iau(on)
+  add(c, "tend_iau", "u", L_EDGE, K);
+  add(c, "tend_iau", "theta", L_CELL, K);
+  add(c, "tend_iau", "rho", L_CELL, K);
+  add(c, "tend_iau", "scalars", L_CELL, (int64_t)ns * K);
+  c.fields.back().nsub = ns;
+  add(c, "scratch", "iau_ru", L_EDGE, K);
+  add(c, "scratch", "iau_rtheta", L_CELL, K);
+  add(c, "scratch", "iau_rho", L_CELL, K);
+  for (const char* n : {"tend_iau.u", "tend_iau.theta", "tend_iau.rho", "tend_iau.scalars", "scratch.iau_ru",
+                        "scratch.iau_rtheta", "scratch.iau_rho"})
+    c.fields[c.by_name[n]].lazy = true;
   // the maxEdges- and maxEdges2-strided mesh arrays (pack_mesh)
   for (const char* n : {"edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "coeffs_reconstruct",
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
@@ -500,6 +523,16 @@ T* P(mpas_dyc_ctx* c, Block& b, const char* pool, const char* name, int tl = 1) 
     abort();
   }
   return (T*)(f->packed ? f->packed : f->buf[slot_of(c, *f, tl)]);
+}
+
+// DO_PHYSICS coupling of the step: the host's flag, or implied by the incremental analysis update
+bool physics_tendencies(const mpas_dyc_ctx* c) { return (c->physics & MPAS_DYC_PHYSICS_TENDENCIES) || c->iau_on; }
+// the step being enqueued applies the IAU forcing (mpas_atm_iau.F:118)
+bool iau_active(const mpas_dyc_ctx* c) { return c->iau_on && c->iau_wgt > 1.0e-12; }
+// Ptrs::tend_*_physics are the library's sums (scratch.iau_*): in a forced step, and in every step of
+// a host that supplies no physics tendencies (then they hold the zeros it would have supplied)
+bool iau_sums(const mpas_dyc_ctx* c) {
+  return c->iau_on && (iau_active(c) || !(c->physics & MPAS_DYC_PHYSICS_TENDENCIES));
 }
 
 Ptrs make_ptrs(mpas_dyc_ctx* c, Block& b) {
@@ -543,6 +576,11 @@ Ptrs make_ptrs(mpas_dyc_ctx* c, Block& b) {
   p.tend_rtheta_physics = P<double>(c, b, "tend_physics", "tend_rtheta_physics");
   p.tend_rho_physics = P<double>(c, b, "tend_physics", "tend_rho_physics");
   p.rqvdynten = P<double>(c, b, "tend_physics", "rqvdynten");
+  if (iau_sums(c)) {  // the step's consumers read physics + IAU (iau.hip), not the host's arrays
+    p.tend_ru_physics = P<double>(c, b, "scratch", "iau_ru");
+    p.tend_rtheta_physics = P<double>(c, b, "scratch", "iau_rtheta");
+    p.tend_rho_physics = P<double>(c, b, "scratch", "iau_rho");
+  }
   SC(delsq_theta); SC(delsq_w); SC(delsq_divergence); SC(delsq_u); SC(delsq_vorticity); SC(dpdz);
   SC(ke_vertex); SC(ke_edge); SC(horiz_flux_array);
   SC(s_max); SC(s_min); SC(scale_arr); SC(flux_arr); SC(flux_upwind_tmp); SC(flux_tmp); SC(wdtn); SC(rho_zz_int);
@@ -617,6 +655,17 @@ inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + WAVES_PER_BLOCK - 
   } while (0)
 
 // captured steps bake pointers, list lengths and flags in: drop them when any of those changes
+void drop_graphs(mpas_dyc_ctx* ctx);
+// the tend_iau pool of a block, zeroed (sums: and the step's physics + IAU arrays, scratch.iau_*)
+int iau_alloc(mpas_dyc_ctx* ctx, Block& b, bool sums) {
+  for (auto& f : b.fields) {
+    if (f.buf[0] || !(f.pool == "tend_iau" || (sums && f.pool == "scratch" && f.name.compare(0, 4, "iau_") == 0))) continue;
+    const int64_t nb = field_bytes(b, f) + 256;
+    HIPCHK(hipMalloc(&f.buf[0], nb));
+    HIPCHK(hipMemset(f.buf[0], 0, nb));
+  }
+  return MPAS_DYC_OK;
+}
 void drop_graphs(mpas_dyc_ctx* ctx) {
   for (auto& kv : ctx->graphs)
     if (kv.second) (void)hipGraphExecDestroy(kv.second);
@@ -1478,6 +1527,43 @@ int lbc_scalars(mpas_dyc_ctx* ctx, const std::vector<Ptrs>& P, double dt, double
   return MPAS_DYC_OK;
 }
 
+// atm_add_tend_anal_incr (mpas_atm_iau.F:81-217) of every block: physics + IAU into scratch.iau_*,
+// which P's tend_*_physics point at (make_ptrs), and into tend.scalars_tend in place.  Reads the
+// host's tend_physics arrays themselves (nullptr, read as 0.0, when the host supplies none).
+int iau_add_tend(mpas_dyc_ctx* ctx, const std::vector<Ptrs>& P) {
+  if (ctx->planning) return MPAS_DYC_OK;
+  const bool host_phys = (ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES) != 0;
+  for (size_t ib = 0; ib < ctx->blk.size(); ++ib) {
+    Block& b = ctx->blk[ib];
+    const Dims& d = b.d;
+    const Ptrs& p = P[ib];
+    const double* u_amb = (const double*)find(b, "tend_iau", "u")->buf[0];
+    const int64_t ne = (int64_t)(d.nEdges + 1) * d.K, nc = (int64_t)(d.nCells + 1) * d.K;
+    auto grid = [](int64_t n) {
+      return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + IAU_THREADS - 1) / IAU_THREADS, IAU_MAX_BLOCKS)));
+    };
+    hipLaunchKernelGGL(k_iau_edges, grid(ne / 2), dim3(IAU_THREADS), 0, ctx->stream, ne, (int64_t)d.nEdgesSolve * d.K,
+                       ctx->iau_wgt, (const double*)p.rho_edge, u_amb,
+                       host_phys ? ::P<const double>(ctx, b, "tend_physics", "tend_ru_physics") : nullptr, p.tend_ru_physics);
+    IauCells a{};
+    a.n = a.plane = nc;
+    a.n_solve = (int64_t)d.nCellsSolve * d.K;
+    a.ns = d.ns, a.moist_start = d.moist_start, a.moist_end = d.moist_end, a.index_qv = ctx->index_qv;
+    a.st_zero = host_phys ? 0 : 1;
+    a.wgt = ctx->iau_wgt;
+    a.zz = p.zz, a.rho_zz = p.rho_zz1, a.theta_m = p.theta_m1, a.scalars = p.scalars1;
+    a.rho_amb = (const double*)find(b, "tend_iau", "rho")->buf[0];
+    a.theta_amb = (const double*)find(b, "tend_iau", "theta")->buf[0];
+    a.scalars_amb = (const double*)find(b, "tend_iau", "scalars")->buf[0];
+    a.phys_rtheta = host_phys ? ::P<const double>(ctx, b, "tend_physics", "tend_rtheta_physics") : nullptr;
+    a.phys_rho = host_phys ? ::P<const double>(ctx, b, "tend_physics", "tend_rho_physics") : nullptr;
+    a.out_rtheta = p.tend_rtheta_physics, a.out_rho = p.tend_rho_physics, a.scalars_tend = p.scalars_tend;
+    if (nc & 1) hipLaunchKernelGGL(k_iau_cells<false>, grid(nc), dim3(IAU_THREADS), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(k_iau_cells<true>, grid(nc / 2), dim3(IAU_THREADS), 0, ctx->stream, a);
+  }
+  return MPAS_DYC_OK;
+}
+
 // The end of atm_srk3 after the microphysics (1650-1660): the regional reset of the specified
 // zone, "because microphysics has messed with them" (1672-1790), then summarize_timestep (1794) --
 // its reductions on the device, the log lines on the host.
@@ -1546,6 +1632,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
   EACH(if (pair_layout(d)) LAUNCH_PE((k_moist_edges_p<false>), (k_moist_edges_p<true>), d.nEdges, d, p);
        else LAUNCH(k_moist_edges, d.nEdges, d, p));
   // physics tendencies are zero without DO_PHYSICS (450-457): scratch arrays stay zero.
+  if (iau_active(ctx)) CHK(iau_add_tend(ctx, P));                 // 459-469: atm_add_tend_anal_incr
 
   // Deferred exchanges.  With split-phase exchanges, the exchange after the diagnostics
   // (1234-1249) runs on the exchange stream while the next kernels that do not read its fields
@@ -1845,7 +1932,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
     }
   }
   EACH(reconstruct(ctx, d, p, p.u2));                              // mpas_reconstruct (1581-1603)
-  if (ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES) {                // DO_PHYSICS block, 1610-1648
+  if (physics_tendencies(ctx)) {                                   // DO_PHYSICS block, 1610-1648
     // rqvdynten (1629-1643) for cu_grell_freitas / cu_tiedtke / cu_ntiedtke, from the scalars before
     // the clip; the microphysics call itself (1650-1660) belongs to the host, after this step
     if (ctx->physics & MPAS_DYC_PHYSICS_RQVDYNTEN)
@@ -2312,7 +2399,13 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
   }
   const int slot = slot_of(ctx, *f, time_level);
   HIPCHK(hipSetDevice(ctx->device));
-  if (f->lazy && !f->buf[slot]) HIPCHK(hipMalloc(&f->buf[slot], nb + 256));
+  if (f->lazy && !f->buf[slot]) {
+    HIPCHK(hipMalloc(&f->buf[slot], nb + 256));
+    if (f->pool == "tend_iau") {  // the pool is whole once one field is set: the others are zero until set
+      HIPCHK(hipMemset(f->buf[slot], 0, nb + 256));
+      CHK(iau_alloc(ctx, b, false));
+    }
+  }
   if (f->me) ctx->bnd_ready = false;  // pack_mesh copies the new image for the kernels
   if (f->is_int && f->target != T_NONE) {
     // MPAS 1-based -> device 0-based; out-of-range / 0 -> garbage slot
@@ -2801,8 +2894,39 @@ int mpas_dyc_set_physics(mpas_dyc_ctx* ctx, int32_t flags) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->physics = flags;
-  for (auto& b : ctx->blk) b.d.physics = (flags & MPAS_DYC_PHYSICS_TENDENCIES) ? 1 : 0;
+  for (auto& b : ctx->blk) b.d.physics = physics_tendencies(ctx) ? 1 : 0;
+  ctx->iau_stale = ctx->iau_on != 0;
   drop_graphs(ctx);  // captured steps bake the flags in
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_set_iau(mpas_dyc_ctx* ctx, int32_t on, double window_length_s) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (on && !(window_length_s > 0.0)) {
+    ctx->err = "mpas_dyc_set_iau: config_IAU_window_length_s must be positive";
+    return MPAS_DYC_EINVAL;
+  }
+  ctx->iau_on = on ? 1 : 0;
+  ctx->iau_window = on ? window_length_s : 0.0;
+  ctx->iau_wgt = 0.0;
+  if (ctx->host_only) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  for (auto& b : ctx->blk) {
+    if (on) CHK(iau_alloc(ctx, b, true));
+    b.d.physics = physics_tendencies(ctx) ? 1 : 0;
+  }
+  ctx->iau_stale = on != 0;
+  drop_graphs(ctx);  // captured steps bake the flag, the weight and the tendencies' pointers in
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_iau_weight(const mpas_dyc_ctx* ctx, double dt, int32_t itimestep, double* wgt) {
+  if (!ctx || !wgt || !(dt > 0.0)) return MPAS_DYC_EINVAL;
+  *wgt = 0.0;
+  if (!ctx->iau_on) return MPAS_DYC_OK;
+  const long nsteps_iau = std::lround(ctx->iau_window / dt);  // nint: halves away from zero
+  if (itimestep <= nsteps_iau) *wgt = 1.0 / ctx->iau_window;
   return MPAS_DYC_OK;
 }
 
@@ -3070,10 +3194,23 @@ int mpas_dyc_output_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level) {
 static int timestep_enqueue(mpas_dyc_ctx* ctx, double dt);
 
 int mpas_dyc_timestep(mpas_dyc_ctx* ctx, double dt, int32_t itimestep) {
-  (void)itimestep;
   if (!ctx || !(dt > 0.0)) return MPAS_DYC_EINVAL;
   if (ctx->host_only) return MPAS_DYC_ESTATE;
   HIPCHK(hipSetDevice(ctx->device));
+  // atm_iau_coef of this step (mpas_atm_iau.F:22-78): which of the two captured steps runs, never a
+  // reason to capture again (the weight is the same for every forced step)
+  CHK(mpas_dyc_iau_weight(ctx, dt, itimestep, &ctx->iau_wgt));
+  if (iau_active(ctx)) {
+    ctx->iau_stale = true;
+  } else if (ctx->iau_on && ctx->iau_stale && !(ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES)) {
+    // an unforced step of a host that supplies no tendencies reads the library's arrays: zeros
+    for (auto& b : ctx->blk)
+      for (const char* n : {"scratch.iau_ru", "scratch.iau_rtheta", "scratch.iau_rho", "tend.scalars_tend"}) {
+        Field& f = b.fields[b.by_name[n]];
+        HIPCHK(hipMemsetAsync(f.buf[0], 0, field_bytes(b, f), ctx->stream));
+      }
+    ctx->iau_stale = false;
+  }
   // a one-sided wait that timed out in an earlier step (its status word, copied back after every
   // step) fails this call, so a host that synchronises rarely does not step on with stale halos
   if (ctx->p2p_status_host && __atomic_load_n(ctx->p2p_status_host, __ATOMIC_ACQUIRE)) {
@@ -3094,7 +3231,9 @@ static int timestep_enqueue(mpas_dyc_ctx* ctx, double dt) {
   if (ctx->use_graph) {
     // one captured graph per buffer layout the step starts from; capturing runs srk3, whose
     // rotations move the host's view of the buffers, and a replay repeats them
-    const std::string sig = layout_sig(ctx);
+    // and one per branch of the incremental analysis update: a forced step holds the two IAU kernels
+    // and reads the library's physics + IAU sums, an unforced one holds neither
+    const std::string sig = layout_sig(ctx) + (iau_active(ctx) ? ".iau" : "");
     auto git = ctx->graphs.find(sig);
     if (git == ctx->graphs.end() || ctx->graph_dt[sig] != dt) {
       if (git != ctx->graphs.end() && git->second) (void)hipGraphExecDestroy(git->second);
@@ -3133,6 +3272,7 @@ static int timestep_enqueue(mpas_dyc_ctx* ctx, double dt) {
       }
       ctx->graphs[sig] = ge;
       ctx->graph_dt[sig] = dt;
+      ++ctx->graph_captures;
       HIPCHK(hipGraphLaunch(ge, ctx->stream));  // the capture made the step's rotations already
       ctx->graph_ran = true;
       return MPAS_DYC_OK;
@@ -3157,7 +3297,7 @@ int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on) {
 
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n) {
   if (!ctx || !out || n < 1) return MPAS_DYC_EINVAL;
-  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : 0.0;
+  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : 0.0;
   return MPAS_DYC_OK;
 }
 

@@ -228,6 +228,12 @@ module atm_time_integration
          type(c_ptr), value :: ctx
          integer(c_int32_t), value :: flags
       end function
+      integer(c_int) function mpas_dyc_set_iau(ctx, on, window_length_s) bind(C, name='mpas_dyc_set_iau')
+         import :: c_int, c_ptr, c_int32_t, c_double
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: on
+         real(c_double), value :: window_length_s
+      end function
       integer(c_int) function mpas_dyc_set_summary(ctx, flags) bind(C, name='mpas_dyc_set_summary')
          import :: c_int, c_ptr, c_int32_t
          type(c_ptr), value :: ctx
@@ -282,6 +288,7 @@ module atm_time_integration
    logical, save, private :: wait_every_step = .false.   ! MPAS_DYCORE_WAIT_EVERY_STEP=1 (diagnostics)
    integer(c_int32_t), save, private :: summary_flags = 0, physics_flags = 0
    real (kind=RKIND), save, private :: dt_init = 0.0_RKIND
+   logical, save, private :: iau_sent = .false.          ! the tend_iau pool and config_IAU_* are on the device
    ! atm_dycore_plan_exchanges: the domain context as host-only contexts (no GPU, no uploads)
    logical, save, private :: plan_only = .false.
    integer(c_int64_t), save, private :: plan_id_sum = 0
@@ -325,7 +332,7 @@ module atm_time_integration
 
    private :: check, fatal, xfer, block_dims, read_config, create_domain_context, set_block_lists, &
               upload_block, pools_to_host, count_blocks, device_index, summarize_timestep, sorted_by, &
-              p2p_wanted, dyc_mpi_allgather
+              p2p_wanted, dyc_mpi_allgather, iau_to_device
 
    contains
 
@@ -377,6 +384,8 @@ module atm_time_integration
 #ifdef DO_PHYSICS
       call physics_to_device(domain)
 #endif
+      if (.not. iau_sent) call iau_to_device(domain)
+      ! itimestep decides on the device whether the step is inside the IAU window (atm_iau_coef)
       call check(dyc, mpas_dyc_timestep(dyc, real(dt, c_double), int(itimestep, c_int32_t)), 'mpas_dyc_timestep')
 #ifdef DO_PHYSICS
       if (iand(physics_flags, PHYS_MICROPHYSICS) /= 0) then
@@ -402,6 +411,42 @@ module atm_time_integration
       if (summary_flags /= 0) call summarize_timestep(domain)
       if (wait_every_step) call check(dyc, mpas_dyc_synchronize(dyc), 'mpas_dyc_synchronize')
    end subroutine atm_srk3
+
+   ! The incremental analysis update (459-469 -> atm_add_tend_anal_incr, mpas_atm_iau.F): with
+   ! config_IAU_option other than 'off', the analysis increments the `iau` stream read into the
+   ! tend_iau pool go to the device once, before the first step, with config_IAU_window_length_s; the
+   ! device then forms the IAU tendencies itself in every step of the window (mpas_dyc_set_iau).
+   ! config_IAU_window_length_s is read only then: a driver without IAU need not define it.
+   subroutine iau_to_device(domain)
+      type (domain_type), intent(inout) :: domain
+      type (block_type), pointer :: block
+      type (mpas_pool_type), pointer :: tend_iau
+      character (len=StrKIND), pointer :: config_IAU_option
+      real (kind=RKIND), pointer :: config_IAU_window_length_s
+      integer :: ib
+
+      iau_sent = .true.
+      nullify(config_IAU_option)
+      call mpas_pool_get_config(domain % blocklist % configs, 'config_IAU_option', config_IAU_option)
+      if (.not. associated(config_IAU_option)) return
+      if (trim(config_IAU_option) == 'off') return
+      call mpas_pool_get_config(domain % blocklist % configs, 'config_IAU_window_length_s', config_IAU_window_length_s)
+      ib = 0
+      block => domain % blocklist
+      do while (associated(block))
+         nullify(tend_iau)
+         call mpas_pool_get_subpool(block % structs, 'tend_iau', tend_iau)
+         if (associated(tend_iau)) then
+            call xfer(dyc, ib, tend_iau, 'tend_iau', 'u', 1, 1, UP, .true.)
+            call xfer(dyc, ib, tend_iau, 'tend_iau', 'theta', 1, 1, UP, .true.)
+            call xfer(dyc, ib, tend_iau, 'tend_iau', 'rho', 1, 1, UP, .true.)
+            call xfer(dyc, ib, tend_iau, 'tend_iau', 'scalars', 1, 1, UP, .true.)
+         end if
+         ib = ib + 1
+         block => block % next
+      end do
+      call check(dyc, mpas_dyc_set_iau(dyc, 1_c_int32_t, real(config_IAU_window_length_s, c_double)), 'mpas_dyc_set_iau')
+   end subroutine iau_to_device
 
    ! Copy the device state into the host pools' time level 1 (the current one once the caller
    ! has shifted time levels after the step): prognostics, diagnostics, rthdynten / rqvdynten.

@@ -28,7 +28,7 @@ EXPORTS = (
     "mpas_dyc_get_block_summary", "mpas_dyc_block_layout", "mpas_dyc_set_profile", "mpas_dyc_get_profile",
     "mpas_dyc_last_exchange", "mpas_dyc_rccl_version", "mpas_dyc_model_init", "mpas_dyc_set_exchange_positions",
     "mpas_dyc_init_deriv_two", "mpas_dyc_init_zb", "mpas_dyc_init_reconstruct", "mpas_dyc_comm_check",
-    "mpas_dyc_fused_tend_acoustic",
+    "mpas_dyc_fused_tend_acoustic", "mpas_dyc_set_iau", "mpas_dyc_iau_weight",
 )
 HOST_ONLY = -2  # MPAS_DYC_HOST_ONLY: planner-only context
 PRINT_GLOBAL_MINMAX_VEL, PRINT_DETAILED_MINMAX_VEL, PRINT_GLOBAL_MINMAX_SCA = 1, 2, 4
@@ -127,6 +127,8 @@ def load() -> C.CDLL:
     lib.mpas_dyc_synchronize.argtypes = [vp]
     lib.mpas_dyc_output_diagnostics.argtypes = [vp, i32]
     lib.mpas_dyc_set_physics.argtypes = [vp, i32]
+    lib.mpas_dyc_set_iau.argtypes = [vp, i32, dbl]
+    lib.mpas_dyc_iau_weight.argtypes = [vp, dbl, i32, C.POINTER(dbl)]
     lib.mpas_dyc_time_acoustic_step.argtypes = [vp, dbl, i32, i32, C.POINTER(dbl), C.POINTER(dbl)]
     lib.mpas_dyc_use_graph.argtypes = [vp, i32]
     lib.mpas_dyc_acoustic_bytes.argtypes = [vp]

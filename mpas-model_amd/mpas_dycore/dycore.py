@@ -329,7 +329,7 @@ class Dycore:
                 for name, a in lm.items():
                     self.set_raw("mesh", name, to_fortran({**case, name: a}, name), block=block)
         for name in case:
-            if name in _SKIP or (device_init and name in MODEL_INIT_OUT) or (device_rec and name == "coeffs_reconstruct"):
+            if name in _SKIP or name in F.IAU_FIELD or (device_init and name in MODEL_INIT_OUT) or (device_rec and name == "coeffs_reconstruct"):
                 continue
             if name in F.LOCATION or name in F.VERTICAL_1D:
                 if name in F.VERTICAL_1D:
@@ -342,6 +342,9 @@ class Dycore:
             self.set_raw("state", name, to_fortran(case, name), 1, block)
         for name in DIAG_INPUTS:
             self.set_raw("diag", name, to_fortran(case, name), block=block)
+        for name, field in F.IAU_FIELD.items():  # the analysis increments, when the case carries them
+            if name in case:
+                self.set_raw("tend_iau", field, to_fortran(case, name), block=block)
 
     # -------------------------------------------------------- operators
     def init_diagnostics(self, dt: float):
@@ -375,6 +378,28 @@ class Dycore:
         flags = ((self.PHYSICS_TENDENCIES if tendencies else 0) | (self.PHYSICS_RQVDYNTEN if rqvdynten else 0)
                  | (self.PHYSICS_MICROPHYSICS if microphysics else 0))
         self._check(self.lib.mpas_dyc_set_physics(self.h, flags), "set_physics")
+
+    def set_iau(self, on: bool, window_length_s: float = 21600.0):
+        """config_IAU_option / config_IAU_window_length_s (mpas_dyc_set_iau): the incremental analysis
+        update of atm_srk3 (mpas_atm_iau.F).  The increments are the ``tend_iau`` pool -- ``u``, ``theta``,
+        ``rho``, ``scalars`` through set / set_raw, or a case's ``u_amb``, ``theta_amb``, ``rho_amb``,
+        ``scalars_amb`` (mpas_files.read_iau), which the constructor uploads.  Steps with itimestep <=
+        nint(window_length_s / dt) are forced.  While on, the step runs as with
+        set_physics(tendencies=True), with zero tendencies if the host supplies none."""
+        self._check(self.lib.mpas_dyc_set_iau(self.h, 1 if on else 0, float(window_length_s)), "set_iau")
+
+    def iau_weight(self, dt: float, itimestep: int) -> float:
+        """atm_iau_coef (mpas_atm_iau.F:22-78): the weight of step ``itimestep``, 0.0 outside the
+        window or with IAU off."""
+        w = C.c_double()
+        self._check(self.lib.mpas_dyc_iau_weight(self.h, float(dt), int(itimestep), C.byref(w)), "iau_weight")
+        return w.value
+
+    def graph_captures(self) -> int:
+        """Steps captured into a hipGraph since the context was created (mpas_dyc_get_profile out[5])."""
+        out = (C.c_double * 6)()
+        self._check(self.lib.mpas_dyc_get_profile(self.h, out, 6), "get_profile")
+        return int(out[5])
 
     def finish_step(self, dt: float):
         """The end of atm_srk3 after the host's microphysics (1672-1794); a no-op unless

@@ -36,6 +36,11 @@ INDEX_TARGET = {
 ONE_BASED_SMALL = {"kiteForCell"}
 COUNTS = {"nEdgesOnCell", "nEdgesOnEdge", "nAdvCellsForEdge", "indexToCellID"}
 
+# the analysis increments of the incremental analysis update as a case carries them -> their field
+# in the tend_iau pool (Registry.xml:3101-3132: name "tend_u", name_in_code "u", ...)
+IAU_FIELD = {"u_amb": "u", "theta_amb": "theta", "rho_amb": "rho", "scalars_amb": "scalars"}
+LOCATION.update(u_amb="edge", theta_amb="cell", rho_amb="cell", scalars_amb="cell")
+
 VERTICAL_1D = ("fzm", "fzp", "rdzw", "rdzu", "u_init", "v_init")
 SCALARS_0D = ("cf1", "cf2", "cf3")
 

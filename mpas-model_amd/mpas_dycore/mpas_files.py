@@ -192,3 +192,59 @@ def read_init(path: str, config: dict | None = None, scalar_names=None, record: 
     if "config_dt" in cfg:
         case["dt"] = float(cfg["config_dt"])
     return case
+
+
+# the `iau` input stream (Registry.xml:1092-1102): xtime and the tend_iau pool (:3101-3132), one
+# Time record -- the analysis-minus-background increments of the incremental analysis update
+IAU_FIXED = {"u_amb": ("nEdges", "nVertLevels"), "rho_amb": ("nCells", "nVertLevels"),
+             "theta_amb": ("nCells", "nVertLevels")}
+
+
+def write_iau(path: str, u_amb, theta_amb, rho_amb, scalars_amb, scalar_names=None, version: int = 2,
+              xtime: str = "0000-01-01_00:00:00") -> None:
+    """An `iau` stream file (x1.N.AmB.<time>.nc): u_amb (nEdges, K), theta_amb and rho_amb (nCells, K)
+    and one q*_amb variable per constituent of scalars_amb (nCells, K, ns), named after
+    ``scalar_names`` (default qv, qc, qr, ...; None in the list: that constituent is left out, as
+    the reference leaves out a variable whose package is inactive)."""
+    u_amb, theta_amb, rho_amb, scalars_amb = (np.asarray(a, dtype=np.float64)
+                                              for a in (u_amb, theta_amb, rho_amb, scalars_amb))
+    ds = ncio.Dataset(unlimited="Time")
+    ds.dims.update(nCells=theta_amb.shape[0], nEdges=u_amb.shape[0], nVertLevels=theta_amb.shape[1], StrLen=64)
+    ds.add("xtime", ("Time", "StrLen"), np.frombuffer(xtime.encode().ljust(64), dtype="S1")[None])
+    for n, a in (("u_amb", u_amb), ("rho_amb", rho_amb), ("theta_amb", theta_amb)):
+        ds.add(n, ("Time",) + IAU_FIXED[n], np.ascontiguousarray(a)[None])
+    ns = scalars_amb.shape[2]
+    names = list(scalar_names) if scalar_names is not None else list(DEFAULT_SCALARS[:ns])
+    if len(names) != ns:
+        raise ValueError(f"write_iau: {ns} constituents, {len(names)} names")
+    for i, n in enumerate(names):
+        if n is not None:
+            ds.add(f"{n}_amb", ("Time", "nCells", "nVertLevels"), np.ascontiguousarray(scalars_amb[:, :, i])[None])
+    ncio.write(path, ds, version=version)
+
+
+def read_iau(path: str, scalar_names, record: int = 0) -> dict:
+    """The increments of an `iau` stream file as case entries: u_amb (nEdges, K), theta_amb, rho_amb
+    (nCells, K) and scalars_amb (nCells, K, len(scalar_names)), constituent i from the variable
+    ``<scalar_names[i]>_amb``; a q*_amb variable the file lacks is zero (its package was inactive when
+    the file was written).  Elements in the file's order, which is the mesh file's, as with read_init.
+    Merge the result into the case (``case.update(read_iau(...))``) before building the Dycore or
+    decomposing: decomp.decompose slices the increments per block, and Dycore uploads them to the
+    tend_iau pool."""
+    ds = ncio.read(path)
+
+    def rec(n):
+        a = np.asarray(ds[n], dtype=np.float64)
+        return np.ascontiguousarray(a[record] if ds.vars[n].dims[0] == ds.unlimited else a)
+
+    missing = [n for n in IAU_FIXED if n not in ds]
+    if missing:
+        raise KeyError(f"{path} is not an iau file: missing {missing}")
+    out = {n: rec(n) for n in IAU_FIXED}
+    nC, K = out["theta_amb"].shape
+    sc = np.zeros((nC, K, len(scalar_names)))
+    for i, n in enumerate(scalar_names):
+        if f"{n}_amb" in ds:
+            sc[:, :, i] = rec(f"{n}_amb")
+    out["scalars_amb"] = sc
+    return out
