@@ -92,7 +92,8 @@ const char* mpas_dyc_last_error(const mpas_dyc_ctx* ctx);
 
 /* Host <-> device copy of one named pool field (pool: "mesh","state","diag","tend",
  * "tend_physics", "lbc", "tend_iau" -- see mpas_dyc_set_iau; scalars 0-d fields cf1/cf2/cf3 take 8
- * bytes). nbytes must match. */
+ * bytes). nbytes must match.  diag.w_velocity_max / wind_speed_level1_max / updraft_helicity_max: see
+ * mpas_dyc_set_diag_update. */
 int mpas_dyc_set_field(mpas_dyc_ctx* ctx, const char* pool, const char* name, int32_t time_level,
                        const void* host, int64_t nbytes);
 int mpas_dyc_get_field(mpas_dyc_ctx* ctx, const char* pool, const char* name, int32_t time_level,
@@ -194,6 +195,55 @@ int mpas_dyc_iau_weight(const mpas_dyc_ctx* ctx, double dt, int32_t itimestep, d
 /* The end of atm_srk3 after the host's microphysics (see MPAS_DYC_PHYSICS_MICROPHYSICS); call it
  * before mpas_dyc_shift_time_levels.  Asynchronous. */
 int mpas_dyc_finish_step(mpas_dyc_ctx* ctx, double dt);
+/* The convective running maxima between history writes: mpas_atm_diag_update (mpas_atm_core.F:700) ->
+ * convective_diagnostics_update (diagnostics/convective_diagnostics.F:99-198), on the device, so a run
+ * that writes them need not copy the state to the host after every step.  The fields are
+ *   diag.w_velocity_max, diag.wind_speed_level1_max, diag.updraft_helicity_max, each (nCells+1);
+ * they are allocated, zeroed, at the first mpas_dyc_set_field of one of them or at
+ * mpas_dyc_set_diag_update with a non-zero mask -- a context that asks for neither holds none of them
+ * and behaves as before -- and mpas_dyc_set_field / get_field / field_bytes / field_device_ptr work on
+ * them from then on (a restart puts them back with set_field).
+ * mpas_dyc_set_diag_update(flags): which maxima mpas_dyc_diag_update advances, the reference's
+ * is_needed_* switches (:33-35, :71-83). Unknown bits: MPAS_DYC_EINVAL.  On a MPAS_DYC_HOST_ONLY context the
+ * mask is kept and nothing is allocated. */
+#define MPAS_DYC_DIAG_W_VELOCITY_MAX 1           /* is_needed_w_max */
+#define MPAS_DYC_DIAG_WIND_SPEED_LEVEL1_MAX 2    /* is_needed_lml_wsp_max */
+#define MPAS_DYC_DIAG_UPDRAFT_HELICITY_MAX 4     /* is_needed_updraft_helicity */
+int mpas_dyc_set_diag_update(mpas_dyc_ctx* ctx, int32_t flags);
+/* convective_diagnostics_update of every block, on the cells 1..nCellsSolve (halo cells and the garbage
+ * slot keep what they hold), from w of time level 1 -- call it after mpas_dyc_shift_time_levels, the
+ * order of mpas_atm_core.F:664-700 -- and from diag.vorticity and diag.uReconstructZonal / Meridional
+ * as the last step (or mpas_dyc_init_diagnostics) left them:
+ *   w_velocity_max        = max(old, maxval(w(1:K)))                 interface K+1 is not part of it (:156)
+ *   wind_speed_level1_max = max(old, sqrt(uz(1)**2 + um(1)**2))                                    (:162)
+ *   updraft_helicity_max  = max(old, uph),
+ *     uph   = sum_k uh(k) max(0, min(z(k+1), 5000) - max(z(k), 2000)),  z(k) = zgrid(k) - zgrid(1),
+ *             added in ascending k from 0.0                                  (integral_zstaggered, :548-565)
+ *     uh(k) = max(0, 0.5 (w(k) + w(k+1))) max(0, zeta(k) / areaCell)                           (:177-178)
+ *     zeta(k) = sum of kiteAreasOnVertex(j,v) vorticity(k,v) over the (v, j) with cellsOnVertex(j,v) =
+ *             the cell, added in ascending block-local v from 0.0, as the reference's scatter over
+ *             the vertices adds them (:169-174) -- not in verticesOnCell order.
+ * Every operation in the Fortran's order (fp64, no contraction), so the result has the reference's
+ * bits for the block's own numbering; a decomposed run's updraft_helicity_max therefore differs from
+ * the one-block run's in the last bits exactly as the reference's does, and the other two do not.
+ * Levels outside the 2-5 km band contribute an exact zero for finite inputs and are skipped, with
+ * their vorticity gathers: an Inf outside the band does not make the sum NaN here.  Results are
+ * guaranteed for finite inputs (Fortran's max with a NaN is unspecified).
+ * MPAS_DYC_DIAG_UPDRAFT_HELICITY_MAX needs mesh.areaCell (the reference divides by it) and
+ * mesh.cellsOnVertex, kiteAreasOnVertex, zgrid: MPAS_DYC_ESTATE if areaCell or cellsOnVertex is not set.
+ * The (v, j) table is derived from cellsOnVertex when the mesh is packed and again after every new
+ * mpas_dyc_set_field of cellsOnVertex.
+ * Asynchronous on the compute stream (synchronous only while mpas_dyc_set_profile is on, which times
+ * it: mpas_dyc_get_profile out[6]); one launch per block, always eager, never part of the step's
+ * captured graph, which stays as it is.  Mask 0: does nothing.  MPAS_DYC_ESTATE between
+ * mpas_dyc_timestep and mpas_dyc_finish_step with MPAS_DYC_PHYSICS_MICROPHYSICS (time level 2 is not
+ * final yet) and on MPAS_DYC_HOST_ONLY contexts. */
+int mpas_dyc_diag_update(mpas_dyc_ctx* ctx);
+/* convective_diagnostics_reset (:501-525), after a history write: the fields named by flags
+ * (MPAS_DYC_DIAG_*) are set to 0.0 over the whole array, halo and garbage slot included, whatever the
+ * update mask is.  Asynchronous.  Unknown bits: MPAS_DYC_EINVAL; fields never allocated: nothing to
+ * do; MPAS_DYC_HOST_ONLY: MPAS_DYC_ESTATE. */
+int mpas_dyc_diag_reset(mpas_dyc_ctx* ctx, int32_t flags);
 /* Regional lateral boundary conditions, config_apply_lbcs (mpas_atm_time_integration.F:683-778,
  * 934-987, 1109-1180, 1253-1270, 1491-1560, 1672-1790; the routines at 6088-6671).  apply = 1 turns
  * them on (the pair kernel layout is required).  The host sets, as in the reference's lbc pool
@@ -453,7 +503,9 @@ double mpas_dyc_acoustic_bytes(const mpas_dyc_ctx* ctx);
  * out[1] = ms of the step (events on the compute stream), out[2] = ms of exposed exchange time,
  * out[3] = RCCL groups issued, out[4] = ms inside them (mostly overlapped with compute).
  * out[5] (profile on or off) = steps captured into a hipGraph since the context was created: it
- * stays put while steps replay (one capture per buffer layout and IAU branch, mpas_dyc_set_iau). */
+ * stays put while steps replay (one capture per buffer layout and IAU branch, mpas_dyc_set_iau).
+ * out[6] = ms of the last mpas_dyc_diag_update called with the profile on (HIP events around its
+ * launches on the compute stream; that call is synchronous). */
 int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on);
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n);
 /* The plan key of the exchange whose RCCL group was enqueued last ("warm_rccl <key>" while the

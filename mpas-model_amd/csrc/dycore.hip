@@ -32,6 +32,7 @@
 #include "lbc.hip"
 #include "model_init.hip"
 #include "iau.hip"
+#include "convdiag.hip"
 
 using namespace mpas;
 
@@ -89,6 +90,12 @@ struct Block {
   std::vector<int32_t> h_coe, h_eoc, h_noc;  // host copies (0-based) for the halo-boundary flags
   std::vector<int32_t> h_voe, h_eov;         // verticesOnEdge / edgesOnVertex (0-based): fused u unpack
   std::vector<int32_t> h_noe;                // nEdgesOnEdge (pack_mesh)
+  // cellsOnVertex (0-based), and the table the convective running maxima derive from it
+  // (convdiag_table): per owned cell its (vertex, j) pairs in ascending vertex index, as 3 v + j
+  std::vector<int32_t> h_cov;
+  int* cv_start = nullptr;
+  int* cv_kite = nullptr;
+  bool cv_ready = false;
   // maxEdges / maxEdges2 as the host declared them (the mesh file's dimensions; Fortran images and
   // h_eoc use these strides).  d.maxEdges / d.maxEdges2 are the strides the kernels index with:
   // max(nEdgesOnCell) and the edgesOnEdge slots the kernels need after pack_mesh
@@ -260,6 +267,12 @@ struct mpas_dyc_ctx {
   double iau_window = 0.0, iau_wgt = 0.0;
   bool iau_stale = false;
   int64_t graph_captures = 0;           // steps captured so far (mpas_dyc_get_profile out[5])
+  // the convective running maxima (mpas_dyc_set_diag_update; convdiag.hip): the MPAS_DYC_DIAG_* mask
+  // mpas_dyc_diag_update applies, and whether diag.w_velocity_max / wind_speed_level1_max /
+  // updraft_helicity_max are allocated (at the first non-zero mask or set_field of one of them)
+  int diag_flags = 0;
+  bool diag_alloc = false;
+  double diag_ms = 0.0;                 // the last mpas_dyc_diag_update under mpas_dyc_set_profile (out[6])
   bool tail_pending = false;            // MPAS_DYC_PHYSICS_MICROPHYSICS: a step ran, mpas_dyc_finish_step not yet
   // exchange profile (mpas_dyc_set_profile): eager steps with HIP events around the exposed part of
   // every exchange (a blocking exchange whole; a split-phase one from the compute stream reaching
@@ -331,6 +344,14 @@ void add(Block& c, const char* pool, const char* name, Loc loc, int64_t inner, i
   f.ntl = ntl;
   c.by_name[f.pool + "." + f.name] = (int)c.fields.size();
   c.fields.push_back(f);
+}
+// the fields of mpas_dyc_diag_update, in the bit order of MPAS_DYC_DIAG_*
+const char* const CONVDIAG_FIELDS[3] = {"w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max"};
+bool is_convdiag(const Field& f) {
+  if (f.pool != "diag") return false;
+  for (const char* n : CONVDIAG_FIELDS)
+    if (f.name == n) return true;
+  return false;
 }
 // The Registry.xml var_structs the dycore touches (same list the oracle harness builds).
 void build_registry(Block& c) {
@@ -495,6 +516,13 @@ void build_registry(Block& c) {
   for (const char* n : {"tend_iau.u", "tend_iau.theta", "tend_iau.rho", "tend_iau.scalars", "scratch.iau_ru",
                         "scratch.iau_rtheta", "scratch.iau_rho"})
     c.fields[c.by_name[n]].lazy = true;
+  // the running maxima of convective_diagnostics_update (Registry.xml diag: (nCells + 1) each):
+  // allocated, zeroed, at the first set_field of one of them or at mpas_dyc_set_diag_update with a
+  // non-zero mask (convdiag_alloc)
+  for (const char* n : CONVDIAG_FIELDS) {
+    add(c, "diag", n, L_CELL, 1);
+    c.fields.back().lazy = true;
+  }
   // the maxEdges- and maxEdges2-strided mesh arrays (pack_mesh)
   for (const char* n : {"edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "coeffs_reconstruct",
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
@@ -673,6 +701,54 @@ void drop_graphs(mpas_dyc_ctx* ctx) {
   ctx->graph_dt.clear();
 }
 
+// The running maxima's derived table of one block: for each owned cell the (vertex, j) pairs with
+// cellsOnVertex(j, vertex) = cell, in ascending vertex index and then j -- the order in which the
+// reference's scatter over the vertices (convective_diagnostics.F:169-174) adds a cell's terms --
+// stored as 3 vertex + j.  Pairs of halo cells and of the garbage cell are dropped.  Rebuilt like
+// the other derived tables: setting cellsOnVertex clears cv_ready (and bnd_ready).
+int convdiag_table(mpas_dyc_ctx* ctx, Block& b) {
+  const Dims& d = b.d;
+  if ((int64_t)b.h_cov.size() < 3LL * d.nVertices) {
+    ctx->err = "mesh.cellsOnVertex not set";
+    return MPAS_DYC_ESTATE;
+  }
+  if (3LL * ((int64_t)d.nVertices + 1) > INT32_MAX) {
+    ctx->err = "too many vertices for the convective diagnostics' table";
+    return MPAS_DYC_EINVAL;
+  }
+  std::vector<int32_t> start((size_t)d.nCellsSolve + 1, 0);
+  for (int64_t i = 0; i < 3LL * d.nVertices; ++i)
+    if (b.h_cov[i] < d.nCellsSolve) ++start[b.h_cov[i] + 1];
+  for (int c = 0; c < d.nCellsSolve; ++c) start[c + 1] += start[c];
+  std::vector<int32_t> fill(start.begin(), start.end() - 1), kite((size_t)std::max(1, start[d.nCellsSolve]));
+  for (int64_t i = 0; i < 3LL * d.nVertices; ++i)  // ascending (vertex, j)
+    if (b.h_cov[i] < d.nCellsSolve) kite[fill[b.h_cov[i]]++] = (int32_t)i;
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // a running update still reads the old table
+  if (b.cv_start) (void)hipFree(b.cv_start);
+  if (b.cv_kite) (void)hipFree(b.cv_kite);
+  b.cv_start = b.cv_kite = nullptr;
+  HIPCHK(hipMalloc(&b.cv_start, start.size() * 4));
+  HIPCHK(hipMalloc(&b.cv_kite, kite.size() * 4));
+  HIPCHK(hipMemcpy(b.cv_start, start.data(), start.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b.cv_kite, kite.data(), kite.size() * 4, hipMemcpyHostToDevice));
+  b.cv_ready = true;
+  return MPAS_DYC_OK;
+}
+
+// diag.w_velocity_max / wind_speed_level1_max / updraft_helicity_max of every block, zeroed
+int convdiag_alloc(mpas_dyc_ctx* ctx) {
+  for (auto& b : ctx->blk)
+    for (auto& f : b.fields) {
+      if (f.buf[0] || !is_convdiag(f)) continue;
+      const int64_t nb = field_bytes(b, f) + 256;
+      HIPCHK(hipMalloc(&f.buf[0], nb));
+      HIPCHK(hipMemsetAsync(f.buf[0], 0, nb, ctx->stream));  // ordered before the stream's updates and resets
+    }
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // and before a set_field / get_field of the caller
+  ctx->diag_alloc = true;
+  return MPAS_DYC_OK;
+}
+
 // Kernel families: 0 "general" (one column per wave, loads where used -- any mesh), 1 "batched"
 // (k_*_b / k_*_r: per-cell records, every load issued up front; maxEdges 6 or 7), 2 "pair"
 // (k_*_p: two edges per wave, two levels per lane; even K).  All three give the same bits
@@ -797,6 +873,7 @@ int compute_bnd(mpas_dyc_ctx* ctx) {
       return MPAS_DYC_ESTATE;
     }
     CHK(pack_mesh(ctx, b));
+    if (ctx->diag_alloc && !b.cv_ready) CHK(convdiag_table(ctx, b));
     if (ctx->lbc && !pair_layout(d)) {
       ctx->err = lbc_layout_error(d);
       return MPAS_DYC_EINVAL;
@@ -2320,6 +2397,8 @@ void mpas_dyc_destroy(mpas_dyc_ctx* ctx) {
     }
     if (b.sum_part) (void)hipFree(b.sum_part);
     if (b.sum_out) (void)hipFree(b.sum_out);
+    if (b.cv_start) (void)hipFree(b.cv_start);
+    if (b.cv_kite) (void)hipFree(b.cv_kite);
   }
   if (ctx->sum_gather) (void)hipFree(ctx->sum_gather);
   p2p_teardown(ctx);  // after the plans (invalidate_plans above) and the field buffers: see there
@@ -2399,6 +2478,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
   }
   const int slot = slot_of(ctx, *f, time_level);
   HIPCHK(hipSetDevice(ctx->device));
+  if (f->lazy && !f->buf[slot] && is_convdiag(*f)) CHK(convdiag_alloc(ctx));  // all three, zeroed
   if (f->lazy && !f->buf[slot]) {
     HIPCHK(hipMalloc(&f->buf[slot], nb + 256));
     if (f->pool == "tend_iau") {  // the pool is whole once one field is set: the others are zero until set
@@ -2427,6 +2507,11 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
     if (f->pool == "mesh" && f->name == "edgesOnCell") {
       b.h_eoc = tmp;
       ctx->bnd_ready = false;
+    }
+    if (f->pool == "mesh" && f->name == "cellsOnVertex") {  // the running maxima's table (convdiag_table)
+      b.h_cov = tmp;
+      b.cv_ready = false;
+      if (ctx->diag_alloc) ctx->bnd_ready = false;
     }
     if (f->pool == "mesh" && (f->name == "verticesOnEdge" || f->name == "edgesOnVertex")) {
       (f->name == "verticesOnEdge" ? b.h_voe : b.h_eov) = tmp;
@@ -2930,6 +3015,97 @@ int mpas_dyc_iau_weight(const mpas_dyc_ctx* ctx, double dt, int32_t itimestep, d
   return MPAS_DYC_OK;
 }
 
+int mpas_dyc_set_diag_update(mpas_dyc_ctx* ctx, int32_t flags) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (flags & ~(CONVDIAG_W | CONVDIAG_WSP | CONVDIAG_UH)) {
+    ctx->err = "mpas_dyc_set_diag_update: unknown flag bits";
+    return MPAS_DYC_EINVAL;
+  }
+  ctx->diag_flags = flags;
+  if (ctx->host_only || !flags) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->diag_alloc) CHK(convdiag_alloc(ctx));
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_diag_update(mpas_dyc_ctx* ctx) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (ctx->host_only) {
+    ctx->err = "host-only context holds no fields";
+    return MPAS_DYC_ESTATE;
+  }
+  if (ctx->tail_pending) {
+    ctx->err = "mpas_dyc_diag_update between mpas_dyc_timestep and mpas_dyc_finish_step";
+    return MPAS_DYC_ESTATE;
+  }
+  if (!ctx->diag_flags) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (ctx->diag_flags & CONVDIAG_UH) {
+    if (!ctx->bnd_ready) CHK(compute_bnd(ctx));  // rebuilds the table after a new cellsOnVertex
+    for (auto& b : ctx->blk) {
+      if (!b.cv_ready) CHK(convdiag_table(ctx, b));
+      if (!find(b, "mesh", "areaCell")->buf[0]) {
+        ctx->err = "mpas_dyc_diag_update: mesh.areaCell not set (MPAS_DYC_DIAG_UPDRAFT_HELICITY_MAX divides by it)";
+        return MPAS_DYC_ESTATE;
+      }
+    }
+  }
+  if (ctx->profile) {
+    for (auto& e : ctx->prof_step)
+      if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(ctx->prof_step[0], ctx->stream));
+  }
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    if (d.nCellsSolve <= 0) continue;
+    ConvDiag a{};
+    a.nCellsSolve = d.nCellsSolve, a.K = d.K, a.flags = ctx->diag_flags;
+    a.w = P<const double>(ctx, b, "state", "w", 1);
+    a.vorticity = P<const double>(ctx, b, "diag", "vorticity");
+    a.uzonal = P<const double>(ctx, b, "diag", "uReconstructZonal");
+    a.umeridional = P<const double>(ctx, b, "diag", "uReconstructMeridional");
+    a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
+    a.areaCell = P<const double>(ctx, b, "mesh", "areaCell");
+    a.kiteAreasOnVertex = P<const double>(ctx, b, "mesh", "kiteAreasOnVertex");
+    a.cv_start = b.cv_start, a.cv_kite = b.cv_kite;
+    a.w_velocity_max = P<double>(ctx, b, "diag", CONVDIAG_FIELDS[0]);
+    a.wind_speed_level1_max = P<double>(ctx, b, "diag", CONVDIAG_FIELDS[1]);
+    a.updraft_helicity_max = P<double>(ctx, b, "diag", CONVDIAG_FIELDS[2]);
+    hipLaunchKernelGGL(k_convdiag, dim3((unsigned)((d.nCellsSolve + CONVDIAG_WAVES - 1) / CONVDIAG_WAVES)),
+                       dim3(CONVDIAG_THREADS), 0, ctx->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  if (ctx->profile) {  // measurement: synchronous, the launches between two events
+    float t = 0.f;
+    HIPCHK(hipEventRecord(ctx->prof_step[1], ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    (void)hipEventElapsedTime(&t, ctx->prof_step[0], ctx->prof_step[1]);
+    ctx->diag_ms = t;
+  }
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_diag_reset(mpas_dyc_ctx* ctx, int32_t flags) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (flags & ~(CONVDIAG_W | CONVDIAG_WSP | CONVDIAG_UH)) {
+    ctx->err = "mpas_dyc_diag_reset: unknown flag bits";
+    return MPAS_DYC_EINVAL;
+  }
+  if (ctx->host_only) {
+    ctx->err = "host-only context holds no fields";
+    return MPAS_DYC_ESTATE;
+  }
+  if (!ctx->diag_alloc) return MPAS_DYC_OK;  // never allocated: zero when they are
+  HIPCHK(hipSetDevice(ctx->device));
+  for (auto& b : ctx->blk)
+    for (int i = 0; i < 3; ++i) {
+      if (!(flags & (1 << i))) continue;
+      Field* f = find(b, "diag", CONVDIAG_FIELDS[i]);
+      HIPCHK(hipMemsetAsync(f->buf[0], 0, field_bytes(b, *f), ctx->stream));
+    }
+  return MPAS_DYC_OK;
+}
+
 int mpas_dyc_model_init(mpas_dyc_ctx* ctx, int32_t h_scale_with_mesh, double config_zd, double config_xnutr) {
   if (!ctx) return MPAS_DYC_EINVAL;
   if (ctx->host_only) return MPAS_DYC_ESTATE;
@@ -3297,7 +3473,7 @@ int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on) {
 
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n) {
   if (!ctx || !out || n < 1) return MPAS_DYC_EINVAL;
-  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : 0.0;
+  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->diag_ms : 0.0;
   return MPAS_DYC_OK;
 }
 

@@ -57,6 +57,13 @@ module atm_time_integration
    ! the state stays in HBM and atm_dycore_to_host copies it when the host reads the pools.
    logical, save :: atm_dycore_sync_every_step = .false.
 
+   ! The convective running maxima on the device (mpas_dyc_diag_update): a mask of 1 = w_velocity_max,
+   ! 2 = wind_speed_level1_max, 4 = updraft_helicity_max (or MPAS_DYCORE_DIAG_UPDATE=<mask>).  Non-zero:
+   ! atm_srk3 advances them after every step, atm_dycore_to_host overwrites the host's arrays with the
+   ! device's, and the driver calls atm_dycore_diag_reset right after mpas_atm_diag_reset
+   ! (INTEGRATION.md).  0 (default): as before, the host's mpas_atm_diag_update is all there is.
+   integer, save :: atm_dycore_diag_update_flags = 0
+
    type, bind(C) :: dyc_dims
       integer(c_int32_t) :: nCells, nEdges, nVertices, nVertLevels, maxEdges, maxEdges2, num_scalars
       integer(c_int32_t) :: nCellsSolve, nEdgesSolve, nVerticesSolve, moist_start, moist_end, index_qv
@@ -234,6 +241,20 @@ module atm_time_integration
          integer(c_int32_t), value :: on
          real(c_double), value :: window_length_s
       end function
+      integer(c_int) function mpas_dyc_set_diag_update(ctx, flags) bind(C, name='mpas_dyc_set_diag_update')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: flags
+      end function
+      integer(c_int) function mpas_dyc_diag_update(ctx) bind(C, name='mpas_dyc_diag_update')
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+      end function
+      integer(c_int) function mpas_dyc_diag_reset(ctx, flags) bind(C, name='mpas_dyc_diag_reset')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: flags
+      end function
       integer(c_int) function mpas_dyc_set_summary(ctx, flags) bind(C, name='mpas_dyc_set_summary')
          import :: c_int, c_ptr, c_int32_t
          type(c_ptr), value :: ctx
@@ -289,6 +310,12 @@ module atm_time_integration
    integer(c_int32_t), save, private :: summary_flags = 0, physics_flags = 0
    real (kind=RKIND), save, private :: dt_init = 0.0_RKIND
    logical, save, private :: iau_sent = .false.          ! the tend_iau pool and config_IAU_* are on the device
+   integer, save, private :: diag_flags_sent = 0         ! the mpas_dyc_set_diag_update mask of the device
+   ! the host's arrays of the running maxima were overwritten with the device's (pools_to_host) after
+   ! the device's last update: only then does a host array of zeros say anything about a reset
+   logical, save, private :: diag_host_current = .false.
+   character(len=32), dimension(3), parameter, private :: diag_max_names = [character(len=32) :: &
+      'w_velocity_max', 'wind_speed_level1_max', 'updraft_helicity_max']   ! bit i-1 of the mask
    ! atm_dycore_plan_exchanges: the domain context as host-only contexts (no GPU, no uploads)
    logical, save, private :: plan_only = .false.
    integer(c_int64_t), save, private :: plan_id_sum = 0
@@ -332,7 +359,7 @@ module atm_time_integration
 
    private :: check, fatal, xfer, block_dims, read_config, create_domain_context, set_block_lists, &
               upload_block, pools_to_host, count_blocks, device_index, summarize_timestep, sorted_by, &
-              p2p_wanted, dyc_mpi_allgather, iau_to_device
+              p2p_wanted, dyc_mpi_allgather, iau_to_device, diag_update_setup
 
    contains
 
@@ -398,6 +425,12 @@ module atm_time_integration
 #endif
       ! the device swaps now; the caller swaps the host pools right after (mpas_atm_core.F:671)
       call check(dyc, mpas_dyc_shift_time_levels(dyc), 'mpas_dyc_shift_time_levels')
+      ! mpas_atm_diag_update's running maxima (mpas_atm_core.F:700) from the new time level 1, on the device
+      if (atm_dycore_diag_update_flags /= diag_flags_sent) call diag_update_setup(domain)
+      if (diag_flags_sent /= 0) then
+         call check(dyc, mpas_dyc_diag_update(dyc), 'mpas_dyc_diag_update')
+         diag_host_current = .false.
+      end if
 #ifdef DO_PHYSICS
       ! the host physics reads the new state every step
       if (iand(physics_flags, PHYS_MICROPHYSICS) == 0 .or. config_apply_lbcs) call pools_to_host(domain, 2, 1)
@@ -447,6 +480,79 @@ module atm_time_integration
       end do
       call check(dyc, mpas_dyc_set_iau(dyc, 1_c_int32_t, real(config_IAU_window_length_s, c_double)), 'mpas_dyc_set_iau')
    end subroutine iau_to_device
+
+   ! The mask of the running maxima to the device, with what the update needs beyond the step's own
+   ! fields -- areaCell, which the reference divides by -- and the host's current values of the
+   ! maxima (zero at a cold start, the restart file's otherwise), so the device goes on from them.
+   subroutine diag_update_setup(domain)
+      type (domain_type), intent(inout) :: domain
+      type (block_type), pointer :: block
+      type (mpas_pool_type), pointer :: mesh, diag
+      integer :: ib, i
+
+      if (atm_dycore_diag_update_flags /= 0) then
+         block => domain % blocklist
+         ib = 0
+         do while (associated(block))
+            call mpas_pool_get_subpool(block % structs, 'mesh', mesh)
+            call mpas_pool_get_subpool(block % structs, 'diag', diag)
+            if (iand(atm_dycore_diag_update_flags, 4) /= 0) call xfer(dyc, ib, mesh, 'mesh', 'areaCell', 1, 1, UP, .true.)
+            do i = 1, size(diag_max_names)
+               if (iand(atm_dycore_diag_update_flags, ishft(1, i - 1)) /= 0 .and. &
+                   iand(diag_flags_sent, ishft(1, i - 1)) == 0) &
+                  call xfer(dyc, ib, diag, 'diag', trim(diag_max_names(i)), 1, 1, UP, .false.)
+            end do
+            ib = ib + 1
+            block => block % next
+         end do
+      end if
+      call check(dyc, mpas_dyc_set_diag_update(dyc, int(atm_dycore_diag_update_flags, c_int32_t)), &
+                 'mpas_dyc_set_diag_update')
+      diag_flags_sent = atm_dycore_diag_update_flags
+   end subroutine diag_update_setup
+
+   ! convective_diagnostics_reset on the device: call it right after mpas_atm_diag_reset in
+   ! atm_core_run (mpas_atm_core.F:744), every step, as that call is.  flags: the MPAS_DYC_DIAG_* bits
+   ! to zero (a driver that knows which fields the streams just wrote passes them).  Without flags the
+   ! routine infers what the host has just reset, and only in a step in which the host's arrays were
+   ! overwritten with the device's after the device's last update (atm_dycore_to_host before the
+   ! write, or the every-step copy): in such a step a host array that is 0.0 on every cell of every
+   ! block was either reset a moment ago (the reference resets a field written by the stream just
+   ! written, convective_diagnostics.F:512-523, and leaves the others running) or is zero on the
+   ! device too, and zeroing the device's copy is right in both cases.  In every other step the
+   ! host's arrays hold stale values -- all zero for a state at rest, whatever the device holds --
+   ! no stream can have written the device's maxima, and nothing is reset.
+   subroutine atm_dycore_diag_reset(domain, flags)
+      type (domain_type), intent(inout) :: domain
+      integer, intent(in), optional :: flags
+      type (block_type), pointer :: block
+      type (mpas_pool_type), pointer :: diag
+      real (kind=RKIND), dimension(:), pointer :: a
+      integer :: mask, i
+
+      if (.not. c_associated(dyc) .or. diag_flags_sent == 0) return
+      if (present(flags)) then
+         mask = flags
+      else
+         if (.not. diag_host_current) return
+         mask = diag_flags_sent
+         block => domain % blocklist
+         do while (associated(block))
+            call mpas_pool_get_subpool(block % structs, 'diag', diag)
+            do i = 1, size(diag_max_names)
+               nullify(a)
+               call mpas_pool_get_array(diag, trim(diag_max_names(i)), a)
+               if (.not. associated(a)) then
+                  mask = iand(mask, not(ishft(1, i - 1)))
+               else if (any(a /= 0.0_RKIND)) then
+                  mask = iand(mask, not(ishft(1, i - 1)))
+               end if
+            end do
+            block => block % next
+         end do
+      end if
+      call check(dyc, mpas_dyc_diag_reset(dyc, int(mask, c_int32_t)), 'mpas_dyc_diag_reset')
+   end subroutine atm_dycore_diag_reset
 
    ! Copy the device state into the host pools' time level 1 (the current one once the caller
    ! has shifted time levels after the step): prognostics, diagnostics, rthdynten / rqvdynten.
@@ -967,6 +1073,13 @@ module atm_time_integration
          do i = N_DIAG_IN + 1, size(diag_names)
             call xfer(dyc, ib, diag, 'diag', trim(diag_names(i)), 1, 1, DOWN, .false.)
          end do
+         ! the running maxima the device keeps: the host's arrays are overwritten with the device's,
+         ! which have every step folded in
+         do i = 1, size(diag_max_names)
+            if (iand(diag_flags_sent, ishft(1, i - 1)) /= 0) &
+               call xfer(dyc, ib, diag, 'diag', trim(diag_max_names(i)), 1, 1, DOWN, .false.)
+         end do
+         if (diag_flags_sent /= 0) diag_host_current = .true.
          call mpas_pool_get_subpool(block % structs, 'tend_physics', tend_physics)
          if (associated(tend_physics)) then
             call xfer(dyc, ib, tend_physics, 'tend_physics', 'rthdynten', 1, 1, DOWN, .false.)
@@ -1224,11 +1337,16 @@ module atm_time_integration
 
    subroutine env_sync_switch()
       character(len=8) :: v
-      integer :: st
+      integer :: st, n
       call get_environment_variable('MPAS_DYCORE_SYNC_EVERY_STEP', v, status=st)
       if (st == 0) atm_dycore_sync_every_step = trim(v) == '1'
       call get_environment_variable('MPAS_DYCORE_WAIT_EVERY_STEP', v, status=st)
       if (st == 0) wait_every_step = trim(v) == '1'
+      call get_environment_variable('MPAS_DYCORE_DIAG_UPDATE', v, status=st)
+      if (st == 0) then
+         read(v, *, iostat=st) n
+         if (st == 0) atm_dycore_diag_update_flags = n
+      end if
    end subroutine env_sync_switch
 
    subroutine block_dims(mesh, state, d)

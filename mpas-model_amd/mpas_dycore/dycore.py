@@ -35,7 +35,8 @@ DIAG_INPUTS = ("theta", "rho", "rho_base", "theta_base")
 _SKIP = set(STATE_INPUTS) | set(DIAG_INPUTS) | {"xCell", "yCell", "zCell", "xEdge", "yEdge", "zEdge", "xVertex",
                                                 "yVertex", "zVertex",
                                                 "latVertex", "lonVertex", "areaCell", "areaTriangle",
-                                                "meshDensity", "indexToCellID", "deriv_two", "zb", "zb3"}
+                                                "meshDensity", "indexToCellID", "deriv_two", "zb", "zb3",
+                                                "w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max"}
 
 
 def _host_allgather_fn(group, nranks: int):
@@ -400,6 +401,42 @@ class Dycore:
         out = (C.c_double * 6)()
         self._check(self.lib.mpas_dyc_get_profile(self.h, out, 6), "get_profile")
         return int(out[5])
+
+    DIAG_FIELDS = ("w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max")
+
+    @staticmethod
+    def _diag_flags(w_max: bool, wsp_max: bool, uh_max: bool) -> int:
+        return ((_lib.DIAG_W_VELOCITY_MAX if w_max else 0) | (_lib.DIAG_WIND_SPEED_LEVEL1_MAX if wsp_max else 0)
+                | (_lib.DIAG_UPDRAFT_HELICITY_MAX if uh_max else 0))
+
+    def set_diag_update(self, w_max: bool = True, wsp_max: bool = True, uh_max: bool = True, flags: int | None = None):
+        """Which convective running maxima diag_update() advances (mpas_dyc_set_diag_update; the
+        reference's is_needed_w_max / is_needed_lml_wsp_max / is_needed_updraft_helicity):
+        ``diag.w_velocity_max``, ``diag.wind_speed_level1_max``, ``diag.updraft_helicity_max``, one value
+        per cell, zero until updated or set (a restart puts them back with set()).  ``flags``: the
+        MPAS_DYC_DIAG_* mask itself instead of the three switches.  The updraft helicity divides by
+        areaCell, which the step itself never reads: it is uploaded here from the case."""
+        if flags is None:
+            flags = self._diag_flags(w_max, wsp_max, uh_max)
+        self._check(self.lib.mpas_dyc_set_diag_update(self.h, int(flags)), "set_diag_update")
+        if flags & _lib.DIAG_UPDRAFT_HELICITY_MAX:
+            for ib, c in enumerate(self.cases):
+                if "areaCell" in c:
+                    self.set_raw("mesh", "areaCell", to_fortran(c, "areaCell"), block=ib)
+
+    def diag_update(self):
+        """mpas_atm_diag_update -> convective_diagnostics_update (convective_diagnostics.F:99-198) on the
+        owned cells of every block, from w of time level 1 and the vorticity and reconstructed winds
+        the last step left: call it after shift_time_levels().  Asynchronous; never part of the
+        step's captured graph.  mpas_dycore.convective.update is its numpy restatement."""
+        self._check(self.lib.mpas_dyc_diag_update(self.h), "diag_update")
+
+    def diag_reset(self, w_max: bool = True, wsp_max: bool = True, uh_max: bool = True, flags: int | None = None):
+        """convective_diagnostics_reset (:501-525), after a history write: the named maxima back to 0.0
+        over the whole array (mpas_dyc_diag_reset)."""
+        if flags is None:
+            flags = self._diag_flags(w_max, wsp_max, uh_max)
+        self._check(self.lib.mpas_dyc_diag_reset(self.h, int(flags)), "diag_reset")
 
     def finish_step(self, dt: float):
         """The end of atm_srk3 after the host's microphysics (1672-1794); a no-op unless

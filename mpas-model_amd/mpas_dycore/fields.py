@@ -41,6 +41,9 @@ COUNTS = {"nEdgesOnCell", "nEdgesOnEdge", "nAdvCellsForEdge", "indexToCellID"}
 IAU_FIELD = {"u_amb": "u", "theta_amb": "theta", "rho_amb": "rho", "scalars_amb": "scalars"}
 LOCATION.update(u_amb="edge", theta_amb="cell", rho_amb="cell", scalars_amb="cell")
 
+# the convective running maxima of mpas_dyc_diag_update (diag pool, one value per cell)
+LOCATION.update(w_velocity_max="cell", wind_speed_level1_max="cell", updraft_helicity_max="cell")
+
 VERTICAL_1D = ("fzm", "fzp", "rdzw", "rdzu", "u_init", "v_init")
 SCALARS_0D = ("cf1", "cf2", "cf3")
 
