@@ -531,6 +531,18 @@ int mpas_dyc_block_layout(mpas_dyc_ctx* ctx, int32_t block, int32_t* out /* [4] 
  * the per-cell records, or MPAS_DYCORE_FUSE_TEND_ACOUSTIC=0).  A first stage of several sub-steps
  * (order 2 with four or more) keeps the two kernels.  Valid once the mesh is set. */
 int mpas_dyc_fused_tend_acoustic(mpas_dyc_ctx* ctx);
+/* Which passes of a step are folded into the kernels that produce their inputs:
+ * bit 0 = the averaging of ruAvg / wwAvg over the dynamics substeps is done by stage 3's last
+ * damping and cell phase, and k_substep_finish_v is not launched (split transport, one block
+ * without exchanges or LBCs, the pair layout with the fused recoveries, at most 63 levels;
+ * MPAS_DYCORE_FOLD_SUBSTEP_AVG=0 turns it off); bit 1 = stage 1's edge kernel also applies the
+ * del4 term and forms the final tend_u, and k_dyn_edges_rk1b_b is not launched (the pair layout,
+ * at most 63 levels, no vertical mixing of u; MPAS_DYCORE_FOLD_RK1_EDGES=0 turns it off);
+ * bit 2 = the w recovery after a stage runs in the launch of the diagnostics' cell kernel
+ * (k_recover3_diag_cells_b; split transport, one block without exchanges or LBCs, the pair layout,
+ * at most 63 levels; MPAS_DYCORE_FUSE_RECOVER_DIAG=0 turns it off).
+ * 0 = none.  Valid once the mesh is set. */
+int mpas_dyc_folded_passes(mpas_dyc_ctx* ctx);
 
 #ifdef __cplusplus
 }

@@ -239,6 +239,15 @@ struct mpas_dyc_ctx {
   // dyn_tend's last cell kernel and the stage's first acoustic cell phase in one launch
   // (k_dyn_cells3_acoustic_r, tend_acoustic_fused); MPAS_DYCORE_FUSE_TEND_ACOUSTIC=0: the two kernels
   bool fuse_tend_acoustic = true;
+  // the substep averaging of ruAvg / wwAvg in stage 3's last damping and cell phase
+  // (substep_avg_folded); MPAS_DYCORE_FOLD_SUBSTEP_AVG=0: k_substep_finish_v
+  bool fold_substep_avg = true;
+  // rk 1's del4 term and final tend_u in k_dyn_edges_p (rk1_edge_folded);
+  // MPAS_DYCORE_FOLD_RK1_EDGES=0: k_dyn_edges_rk1b_b
+  bool fold_rk1_edges = true;
+  // the w recovery and the diagnostics' cell kernel in one launch (k_recover3_diag_cells_b,
+  // recover_diag_fused); MPAS_DYCORE_FUSE_RECOVER_DIAG=0: the two kernels
+  bool fuse_recover_diag = true;
   std::vector<XField> late_fs;
   bool late_pending = false;
   bool fused_pack_enabled = true;       // MPAS_DYCORE_FUSED_PACK=0: pack kernel instead (A/B)
@@ -1075,6 +1084,8 @@ struct TendAcoustic {
   bool fin;  // the stage has one sub-step: the cell phase also recovers the owned cells
   double dts, rdt, invNs;
   int keep_pp, dl, store_tend;
+  int sa;         // the substep averaging of wwAvg in the fused recovery (substep_avg_folded), or 0
+  double sa_inv;
 };
 // Whether stage rk_step of nsub sub-steps runs that launch: nothing lies between the two kernels
 // (no exchange, so no cell with a halo edge is left to k_smlstep_pert_b; no LBC kernels), both are
@@ -1087,6 +1098,43 @@ bool tend_acoustic_fused(const mpas_dyc_ctx* ctx, int rk_step, int nsub) {
   if (!ctx->fuse_tend_acoustic || needs_exchange(ctx) || ctx->lbc || ctx->blk.size() != 1) return false;
   const Dims& d = ctx->blk[0].d;
   return fuse_smlstep(d) && fused_recover(d) && !(rk_step == 1 && nsub > 1);
+#endif
+}
+// Whether stage 3's last damping and cell phase do the substep averaging of ruAvg / wwAvg
+// (store_avg in kernels.hip) and srk3 launches no k_substep_finish_v.  Between their stores and
+// that kernel nothing may read ruAvg / wwAvg (transport outside the dynamics; no exchange, no
+// LBC), and the two kernels must store every element it covers: the pair-layout damping with the
+// fused recoveries, every cell owned and every edge between two owned cells (compute_bnd).
+bool substep_avg_folded(const mpas_dyc_ctx* ctx) {
+#ifdef MPAS_WIDE
+  return false;
+#else
+  if (!ctx->fold_substep_avg || needs_exchange(ctx) || ctx->lbc || ctx->blk.size() != 1) return false;
+  if (!ctx->cf.split_dynamics_transport) return false;
+  const Dims& d = ctx->blk[0].d;
+  return pair_layout(d) && fused_recover(d) && d.nCellsSolve == d.nCells && d.nEdgesSolve == d.nEdges &&
+         d.n_bnd_edges == 0;
+#endif
+}
+// Whether stage 1's edge kernel (k_dyn_edges_p<true, NE2, true, ODD, true>) also does
+// k_dyn_edges_rk1b_b's work on block d; that kernel's vertical mixing of u stays with it
+bool rk1_edge_folded(const mpas_dyc_ctx* ctx, const Dims& d) {
+#ifdef MPAS_WIDE
+  return false;
+#else
+  return ctx->fold_rk1_edges && pair_layout(d) && !(ctx->cf.v_mom_eddy_visc2 > 0.0);
+#endif
+}
+// Whether the w recovery runs in the launch of the diagnostics' cell kernel
+// (k_recover3_diag_cells_b, after k_diag_vertices_p): nothing may lie between the recovery and the
+// diagnostics (no u exchange, no LBC kernel, no transport inside the dynamics); pair layout only
+bool recover_diag_fused(const mpas_dyc_ctx* ctx) {
+#ifdef MPAS_WIDE
+  return false;
+#else
+  if (!ctx->fuse_recover_diag || needs_exchange(ctx) || ctx->lbc || ctx->blk.size() != 1) return false;
+  if (ctx->cf.scalar_advection && !ctx->cf.split_dynamics_transport) return false;
+  return pair_layout(ctx->blk[0].d);
 #endif
 }
 // the sub-steps of each stage (atm_srk3, 296-322)
@@ -1135,12 +1183,37 @@ void dyn_tend(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, int rk_step, doub
     else LAUNCH(k_dyn_cells1_b<7>, d.nCells, d, p, cf, s);
   }
   if (part == 1) return;
+  // rk 1's delsq_divergence / delsq_vorticity (4893-4931) from k_dyn_edges_pgf_p's delsq_u, batched families
+  auto delsq_vc = [&]() {
+    if (!(s.h_mom_eddy_visc4 > 0.0)) return;
+    if (pair_layout(d) && g_delsq_pair) {  // interleaved, PAIR_EPW elements per wavefront
+      const int64_t nw = 3 * std::max<int64_t>((d.nVertices + 2 * PAIR_EPW - 1) / (2 * PAIR_EPW),
+                                               (d.nCells + PAIR_EPW - 1) / PAIR_EPW);
+      if (m6) LAUNCH_PE((k_dyn_delsq_vc_p<6, false>), (k_dyn_delsq_vc_p<6, true>), nw * PAIR_EPW, d, p);
+      else LAUNCH_PE((k_dyn_delsq_vc_p<7, false>), (k_dyn_delsq_vc_p<7, true>), nw * PAIR_EPW, d, p);
+    } else {
+      const int nvc = 3 * std::max((d.nVertices + 1) / 2, d.nCells);  // interleaved (k_dyn_delsq_vc_b)
+      if (m6) LAUNCH(k_dyn_delsq_vc_b<6>, nvc, d, p);
+      else LAUNCH(k_dyn_delsq_vc_b<7>, nvc, d, p);
+    }
+  };
+  // rk 1, pair layout: the edge kernel also does k_dyn_edges_rk1b_b's work (the del4 term, the final
+  // tend_u and the 642 exchange's pack), so it runs after k_dyn_delsq_vc_p, which reads only the
+  // delsq_u of k_dyn_edges_pgf_p and writes nothing the edge kernel read before
+  const bool fold1 = rk_step == 1 && rk1_edge_folded(ctx, d);
   if (pair_layout(d)) {
     const int64_t nw = d.nEdges;
     if (rk_step == 1) LAUNCH_PE((k_dyn_edges_pgf_p<false>), (k_dyn_edges_pgf_p<true>), nw, d, p);
-    if (d.maxEdges == 6 && rk_step == 1) LAUNCH_PE((k_dyn_edges_p<true, 10, true, false>), (k_dyn_edges_p<true, 10, true, true>), nw, d, p, cf, s, 0);
+#ifndef MPAS_WIDE
+    if (fold1) {
+      delsq_vc();
+      if (m6) LAUNCH_PE((k_dyn_edges_p<true, 10, true, false, true>), (k_dyn_edges_p<true, 10, true, true, true>), nw, d, p, cf, s, 1, tp);
+      else LAUNCH_PE((k_dyn_edges_p<true, 12, true, false, true>), (k_dyn_edges_p<true, 12, true, true, true>), nw, d, p, cf, s, 1, tp);
+    }
+#endif
+    if (d.maxEdges == 6 && rk_step == 1 && !fold1) LAUNCH_PE((k_dyn_edges_p<true, 10, true, false>), (k_dyn_edges_p<true, 10, true, true>), nw, d, p, cf, s, 0);
     if (d.maxEdges == 6 && rk_step != 1) LAUNCH_PE((k_dyn_edges_p<false, 10, false, false>), (k_dyn_edges_p<false, 10, false, true>), nw, d, p, cf, s, 1, tp);
-    if (d.maxEdges == 7 && rk_step == 1) LAUNCH_PE((k_dyn_edges_p<true, 12, true, false>), (k_dyn_edges_p<true, 12, true, true>), nw, d, p, cf, s, 0);
+    if (d.maxEdges == 7 && rk_step == 1 && !fold1) LAUNCH_PE((k_dyn_edges_p<true, 12, true, false>), (k_dyn_edges_p<true, 12, true, true>), nw, d, p, cf, s, 0);
     if (d.maxEdges == 7 && rk_step != 1) LAUNCH_PE((k_dyn_edges_p<false, 12, false, false>), (k_dyn_edges_p<false, 12, false, true>), nw, d, p, cf, s, 1, tp);
   } else if (batched(d)) {
     if (d.maxEdges == 6 && rk_step == 1) LAUNCH_E((k_dyn_edges_b<true, 10>), d.nEdges, d, p, cf, s, 0);
@@ -1157,19 +1230,10 @@ void dyn_tend(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, int rk_step, doub
       LAUNCH(k_dyn_edges_rk1b, d.nEdgesSolve, d, p, cf, s);
       LAUNCH(k_dyn_cells2, d.nCells, d, p);
     } else {
-      if (s.h_mom_eddy_visc4 > 0.0) {
-        if (pair_layout(d) && g_delsq_pair) {  // interleaved, PAIR_EPW elements per wavefront
-          const int64_t nw = 3 * std::max<int64_t>((d.nVertices + 2 * PAIR_EPW - 1) / (2 * PAIR_EPW),
-                                                   (d.nCells + PAIR_EPW - 1) / PAIR_EPW);
-          if (m6) LAUNCH_PE((k_dyn_delsq_vc_p<6, false>), (k_dyn_delsq_vc_p<6, true>), nw * PAIR_EPW, d, p);
-          else LAUNCH_PE((k_dyn_delsq_vc_p<7, false>), (k_dyn_delsq_vc_p<7, true>), nw * PAIR_EPW, d, p);
-        } else {
-          const int nvc = 3 * std::max((d.nVertices + 1) / 2, d.nCells);  // interleaved (k_dyn_delsq_vc_b)
-          if (m6) LAUNCH(k_dyn_delsq_vc_b<6>, nvc, d, p);
-          else LAUNCH(k_dyn_delsq_vc_b<7>, nvc, d, p);
-        }
+      if (!fold1) {
+        delsq_vc();
+        LAUNCH(k_dyn_edges_rk1b_b, d.nEdgesSolve, d, p, cf, s, tp);
       }
-      LAUNCH(k_dyn_edges_rk1b_b, d.nEdgesSolve, d, p, cf, s, tp);
       if (pair_layout(d) && g_cells2_pair) {
         if (m6) LAUNCH_PE((k_dyn_cells2_p<6, false>), (k_dyn_cells2_p<6, true>), d.nCells, d, p);
         else LAUNCH_PE((k_dyn_cells2_p<7, false>), (k_dyn_cells2_p<7, true>), d.nCells, d, p);
@@ -1191,7 +1255,7 @@ void dyn_tend(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, int rk_step, doub
     // rho_zz2_rd / theta_m2_rd are this stage's ru / rw / w2 / rho_zz2 / theta_m2, which the
     // tendencies read
     const TendAcArgs a{ta->dts, cf.epssm, ta->rdt, ta->invNs, rk_step, ta->keep_pp, ta->dl,
-                       ta->store_tend};
+                       ta->store_tend, ta->sa, ta->sa_inv};
     const bool m6 = d.maxEdges == 6, fin = ta->fin;
     if (m6 && rk_step == 1) LAUNCH((k_dyn_cells3_acoustic_r<6, true, true>), d.nCells, d, ta->pf, cf, s, a);
     if (m6 && rk_step != 1 && fin) LAUNCH((k_dyn_cells3_acoustic_r<6, false, true>), d.nCells, d, ta->pf, cf, s, a);
@@ -1272,20 +1336,21 @@ void acoustic_edges(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dts,
 // pk: the block's fused-pack map of the exchange that follows (fused_pack_map), or none
 // dl: store rtheta_pp - rtheta_pp_old for the stage's last damping only (damping_delta)
 // rp (fin only): the block's pack map of the 876-887 exchange that follows the stage (XPlan::fused_rec)
+// sa, sa_inv (fin only): the substep averaging of wwAvg in the recovery (substep_avg_folded), or 0
 void acoustic_cells(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dts, int small_step, int fin = 0,
                     double rdt = 0.0, double invNs = 0.0, int rk_step = 0, int keep_pp = 1, PackMap pk = PackMap{},
-                    int dl = 0, XPack rp = XPack{}) {
+                    int dl = 0, XPack rp = XPack{}, int sa = 0, double sa_inv = 0.0) {
   if (batched(d) && d.maxEdges == 6) {
     if (fin)
       LAUNCH((k_acoustic_cells_r<6, true>), d.nCells, d, p, dts, small_step, ctx->cf.epssm, rdt, invNs, rk_step, keep_pp,
-             pk, dl, rp);
+             pk, dl, rp, sa, sa_inv);
     else LAUNCH((k_acoustic_cells_r<6, false>), d.nCells, d, p, dts, small_step, ctx->cf.epssm, 0.0, 0.0, 0, 1, pk);
     return;
   }
   if (batched(d) && d.maxEdges == 7) {
     if (fin)
       LAUNCH((k_acoustic_cells_r<7, true>), d.nCells, d, p, dts, small_step, ctx->cf.epssm, rdt, invNs, rk_step, keep_pp,
-             pk, dl, rp);
+             pk, dl, rp, sa, sa_inv);
     else LAUNCH((k_acoustic_cells_r<7, false>), d.nCells, d, p, dts, small_step, ctx->cf.epssm, 0.0, 0.0, 0, 1, pk);
     return;
   }
@@ -1310,16 +1375,17 @@ bool fused_recover_edges(const Dims& d) { return pair_layout(d) && fused_recover
 // dl: rtheta_pp_old holds the difference (acoustic_cells with dl); pair layout only
 // rp: the block's pack map of the 876-887 exchange (XPlan::fused_rec), or none
 // upk: the block's pack map of the u exchange (988, XPlan::fused_rec), used by the recovering variant
+// sa, sa_inv: the substep averaging of ruAvg by the recovering variant (substep_avg_folded), or 0
 void divergence_damping(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dts, int phase, int fresh = 0,
                         double invNs = 0.0, UnpackMap um = UnpackMap{}, int dl = 0, XPack rp = XPack{},
-                        XPack upk = XPack{}) {
+                        XPack upk = XPack{}, int sa = 0, double sa_inv = 0.0) {
   // (k_divdamp_b, one edge per wave with batched loads, measured 6 % slower than this)
   const bool up = um.recv != nullptr;
   const int64_t nw = phase == 2 ? d.n_bnd_pairs : d.nEdges;  // phase 2: the bnd_pairs list
   const double cd = coef_divdamp(ctx, dts);
   if (pair_layout(d) && invNs > 0.0 && fused_recover_edges(d)) {
-    if (up) LAUNCH_PE((k_divdamp_p<true, true, false>), (k_divdamp_p<true, true, true>), nw, d, p, cd, phase, dts, fresh, invNs, um, dl, rp, upk);
-    else LAUNCH_PE((k_divdamp_p<true, false, false>), (k_divdamp_p<true, false, true>), nw, d, p, cd, phase, dts, fresh, invNs, um, dl, rp, upk);
+    if (up) LAUNCH_PE((k_divdamp_p<true, true, false>), (k_divdamp_p<true, true, true>), nw, d, p, cd, phase, dts, fresh, invNs, um, dl, rp, upk, sa, sa_inv);
+    else LAUNCH_PE((k_divdamp_p<true, false, false>), (k_divdamp_p<true, false, true>), nw, d, p, cd, phase, dts, fresh, invNs, um, dl, rp, upk, sa, sa_inv);
   } else if (pair_layout(d)) {
     if (up) LAUNCH_PE((k_divdamp_p<false, true, false>), (k_divdamp_p<false, true, true>), nw, d, p, cd, phase, dts, fresh, 0.0, um, dl, rp);
     else LAUNCH_PE((k_divdamp_p<false, false, false>), (k_divdamp_p<false, false, true>), nw, d, p, cd, phase, dts, fresh, 0.0, um, dl, rp);
@@ -1333,8 +1399,10 @@ void divergence_damping(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double 
 // overwrites them, so only the last call of a dt (and the model-init call) stores them: the pool
 // holds the same values after the step, at 2 x 8 B per edge-level less traffic in 8 of 9 calls.
 // uu_up: the block's fused-unpack map of the u exchange that precedes (988), or none
+// rec3_hdiv >= 0 (pair layout): the cell kernel's launch also does the w recovery that srk3 then
+// does not launch (recover_diag_fused), with hdiv = rec3_hdiv (see recover_cells3)
 void solve_diagnostics(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dt, int tl, int rk_step /*0 = absent*/,
-                       int store_grad = 1, XUnpack uu_up = XUnpack{}) {
+                       int store_grad = 1, XUnpack uu_up = XUnpack{}, int rec3_hdiv = -1) {
   const double* u = (tl == 1) ? p.u1 : p.u2;
   const double* h = (tl == 1) ? p.rho_zz1 : p.rho_zz2;
   const int reconstruct_v = (rk_step == 0 || rk_step == 3) ? 1 : 0;
@@ -1353,6 +1421,12 @@ void solve_diagnostics(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double d
     // (a pair-layout k_diag_cells, two cells per wave, measured 18 % slower than the batched one; a
     // round-5 version with the edge and vertex sums in two passes, 66 VGPRs, bitwise: 206 against
     // 202 us per call, profiles/r05_ab_diag_cells_pair_rejected.log)
+#ifndef MPAS_WIDE
+    if (rec3_hdiv >= 0) {
+      if (d.maxEdges == 6) LAUNCH(k_recover3_diag_cells_b<6>, d.nCells, d, p, rec3_hdiv, u, ctx->cf.apvm_upwinding, store_dv);
+      else LAUNCH(k_recover3_diag_cells_b<7>, d.nCells, d, p, rec3_hdiv, u, ctx->cf.apvm_upwinding, store_dv);
+    } else
+#endif
     if (d.maxEdges == 6) LAUNCH(k_diag_cells_b<6>, d.nCells, d, p, u, ctx->cf.apvm_upwinding, store_dv);
     else LAUNCH(k_diag_cells_b<7>, d.nCells, d, p, u, ctx->cf.apvm_upwinding, store_dv);
     const int64_t nw = d.nEdges;
@@ -1734,6 +1808,8 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
     rec_overlap = rec_overlap || !fused_recover(b.d) || !fused_recover_edges(b.d);
   }
   if (ctx->overlap_all) sml_fused = false, rec_overlap = true;
+  const bool avg_folded = substep_avg_folded(ctx);
+  const bool rd_fused = recover_diag_fused(ctx);
   EACHV(Ppre, vert_imp_coefs(ctx, d, p, rk_sub_timestep[0]));    // 476-510 of dynamics substep 1
   for (int dynamics_substep = 1; dynamics_substep <= dynamics_split; ++dynamics_substep) {
     // 513 (exner): carried by the step-start exchange and by the 1282-1297 exchange below
@@ -1755,10 +1831,16 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
       // sub-step 1's cell phase in the launch of dyn_tend's last cell kernel (one block; tend_w and
       // tend_theta are stored for a second sub-step or, after the dt's last stage, for the pool)
       const bool fuse_ta = tend_acoustic_fused(ctx, rk_step, nsub);
+      // stage 3's last damping and cell phase average ruAvg / wwAvg over the dynamics substeps
+      const int sa = (avg_folded && rk_step == 3)
+                         ? SA_ON | (dynamics_substep == 1 ? SA_FIRST : 0) | (dynamics_substep == dynamics_split ? SA_LAST : 0)
+                         : 0;
+      const double sa_inv = 1.0 / (double)dynamics_split;
       TendAcoustic ta{};
       if (fuse_ta)
         ta = TendAcoustic{PF[0], nsub == 1, dts, rk_timestep[rk_step - 1], 1 / (double)nsub, last_stage ? 1 : 0,
-                          nsub == 1 ? damping_delta(ctx, ctx->blk[0].d, last_stage) : 0, (nsub > 1 || last_stage) ? 1 : 0};
+                          nsub == 1 ? damping_delta(ctx, ctx->blk[0].d, last_stage) : 0, (nsub > 1 || last_stage) ? 1 : 0,
+                          nsub == 1 ? sa : 0, sa_inv};
       const TendAcoustic* tap = fuse_ta ? &ta : nullptr;
       if (pending) {  // 561-630, k_dyn_cells1 overlapping the exchange
         EACHV(PS, dyn_tend(ctx, d, p, rk_step, dt, 1, hdiv_prev && batched(d)));
@@ -1859,7 +1941,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
               acoustic_cells(ctx, d, p, dts, small_step, small_step == nsub, rk_timestep[rk_step - 1],
                             1 / (double)nsub, rk_step, needs_exchange(ctx) || last_stage,
                             xp ? xp->pack[ib_] : PackMap{}, damping_delta(ctx, d, last_stage),
-                            small_step == nsub ? rpc(ib_) : XPack{}));
+                            small_step == nsub ? rpc(ib_) : XPack{}, small_step == nsub ? sa : 0, sa_inv));
         if (split) {
           CHK(exchange_async(ctx, xf));
         } else {
@@ -1873,7 +1955,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
         EACH(divergence_damping(ctx, d, p, dts, 2, nsub == 1, 0.0, um_of(ib_), 0, rpe(ib_)));
       } else {
         EACH(divergence_damping(ctx, d, p, dts, 0, nsub == 1, 1 / (double)nsub, um_of(ib_),
-                                damping_delta(ctx, d, last_stage), rpe(ib_), upk(ib_)));
+                                damping_delta(ctx, d, last_stage), rpe(ib_), upk(ib_), sa, sa_inv));
       }
       const double invNs = 1 / (double)number_sub_steps[rk_step - 1];
       const double rdt = rk_timestep[rk_step - 1];
@@ -1919,7 +2001,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
         EACH(if (!fused_recover_edges(d)) LAUNCH(k_recover_edges, d.nEdges, d, p, invNs, 0, rue(ib_), upk(ib_));
              else LAUNCH(k_recover_edges, d.n_bnd_edges, d, p, invNs, 2, rue(ib_), upk(ib_)));
         // stages 1 and 2: also the next stage's h_divergence (dyn_tend then skips k_dyn_cells1)
-        EACH(recover_cells3(ctx, d, p, 0, hdiv_next));
+        if (!rd_fused) EACH(recover_cells3(ctx, d, p, 0, hdiv_next));
         if (lbc)  // 934-987
           EACH(LAUNCH(k_lbc_u, d.nEdges, d, p, dt_dynamics * (double)(dynamics_substep - 1) + rk_timestep[rk_step - 1]));
         if (!u_skip) CHK(exchange(ctx, {{"state", "u", 2, ALL_LAYERS}}));  // 988
@@ -1933,7 +2015,8 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
         if (lbc) CHK(lbc_scalars(ctx, P, dt, rk_timestep[rk_step - 1]));  // 1109-1180
       }
       EACH(solve_diagnostics(ctx, d, p, dt, 2, rk_step,             // 1187-1228
-                             dynamics_substep == dynamics_split && rk_step == 3, uup(ib_)));
+                             dynamics_substep == dynamics_split && rk_step == 3, uup(ib_),
+                             rd_fused ? (hdiv_next ? 1 : 0) : -1));
       const unsigned pve_layers = (!lbc && (ctx->halo_trim & 2)) ? 0x3u : ALL_LAYERS;
       std::vector<XField> xd = {{"state", "w", 2, ALL_LAYERS}, {"diag", "pv_edge", 0, pve_layers},  // 1234-1249
                                 {"diag", "rho_edge", 0, pve_layers}};
@@ -1972,7 +2055,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
       }
       hdiv_prev = hdiv_next;
     }
-    if (!ctx->planning)                                           // 1304-1341
+    if (!ctx->planning && !avg_folded)                            // 1304-1341, or done by stage 3's kernels
       EACH(hipLaunchKernelGGL(k_substep_finish_v, dim3(2048), dim3(BLOCK_THREADS), 0, ctx->stream, d, p,
                               dynamics_substep, dynamics_split, 1.0 / (double)dynamics_split));
     if (dynamics_substep < dynamics_split) {  // the saves and theta_m_1 = theta_m_2 of 6051-6058
@@ -2337,6 +2420,9 @@ int mpas_dyc_create_blocks(int32_t nblocks, const mpas_dyc_dims* dims, const mpa
   if (const char* li = getenv("MPAS_DYCORE_LATE_ISSUE")) ctx->late_issue = std::string(li) == "1";
   if (const char* oa = getenv("MPAS_DYCORE_OVERLAP_ALL")) ctx->overlap_all = std::string(oa) == "1";
   if (const char* ft = getenv("MPAS_DYCORE_FUSE_TEND_ACOUSTIC")) ctx->fuse_tend_acoustic = std::string(ft) != "0";
+  if (const char* fs = getenv("MPAS_DYCORE_FOLD_SUBSTEP_AVG")) ctx->fold_substep_avg = std::string(fs) != "0";
+  if (const char* fe = getenv("MPAS_DYCORE_FOLD_RK1_EDGES")) ctx->fold_rk1_edges = std::string(fe) != "0";
+  if (const char* fr = getenv("MPAS_DYCORE_FUSE_RECOVER_DIAG")) ctx->fuse_recover_diag = std::string(fr) != "0";
   if (const char* ov = getenv("MPAS_DYCORE_OVERLAP")) ctx->overlap = std::atoi(ov);
   for (auto& b : ctx->blk) {
     build_registry(b);
@@ -3615,6 +3701,18 @@ int mpas_dyc_fused_tend_acoustic(mpas_dyc_ctx* ctx) {
   stage_sub_steps(ctx->cf, nsub);
   for (int rk = 1; rk <= 3; ++rk)
     if (tend_acoustic_fused(ctx, rk, nsub[rk - 1])) m |= 1 << (rk - 1);
+  return m;
+}
+
+int mpas_dyc_folded_passes(mpas_dyc_ctx* ctx) {
+  if (!ctx || ctx->host_only) return 0;
+  if (hipSetDevice(ctx->device) != hipSuccess) return 0;
+  if (!ctx->bnd_ready && compute_bnd(ctx) != MPAS_DYC_OK) return 0;
+  int m = substep_avg_folded(ctx) ? 1 : 0;
+  bool all = !ctx->blk.empty();
+  for (const auto& b : ctx->blk) all = all && rk1_edge_folded(ctx, b.d);
+  if (all) m |= 2;
+  if (recover_diag_fused(ctx)) m |= 4;
   return m;
 }
 

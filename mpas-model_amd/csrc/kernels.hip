@@ -2142,9 +2142,16 @@ __device__ __forceinline__ void pack_rec_edge(const XPack& pk, const Dims& d, in
 // launch computes tend_u alone and k_dyn_edges_pgf_p the PGF part of tend_u_euler and del2 --
 // at rk1 the two are independent (no finalize), and together they need 244 VGPRs (2 waves/SIMD).
 // tp: with finalize, the final tend_u also goes to the 642 exchange's send buffer (XPack), or nothing
-template <bool RK1, int NE2, bool SPLIT = false, bool ODD = false>
+// DEL4 (rk1 SPLIT, launched with finalize after k_dyn_edges_pgf_p and k_dyn_delsq_vc_p): the owned
+// edges also get k_dyn_edges_rk1b_b's work -- the del4 term of tend_u_euler (4893-4931) and the
+// final tend_u -- on the tend_u, u and rho_edge still in registers, so tend_u is stored once and
+// k_dyn_edges_rk1b_b is not launched (dyn_tend, rk1_edge_folded).  Not with vertical mixing of u.
+// tend_u_euler and the four del4 gathers are loaded after the TRiSK sum has consumed pv[] / uu[]:
+// loaded with them they would add 10 VGPRs to the kernel's peak.
+template <bool RK1, int NE2, bool SPLIT = false, bool ODD = false, bool DEL4 = false>
 __global__ __launch_bounds__(PAIR_THREADS) void k_dyn_edges_p(Dims d, Ptrs p, Config cf, DynTendScal s,
                                                               int finalize, XPack tp = XPack{}) {
+  static_assert(!DEL4 || (RK1 && SPLIT), "DEL4 is the rk1 SPLIT form's finalisation");
   constexpr bool PGF = RK1 && !SPLIT;
   const int eA = PAIR_EPW * pair_wave();
   if (eA >= d.nEdges) return;
@@ -2281,6 +2288,24 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_dyn_edges_p(Dims d, Ptrs p, Co
   }
   tu.x = tu.x + re.x * (q.x - (ke2.x - ke1.x) * invDc) - uk.x * 0.5 * (hd1.x + hd2.x);
   tu.y = tu.y + re.y * (q.y - (ke2.y - ke1.y) * invDc) - uk.y * 0.5 * (hd1.y + hd2.y);
+  if (DEL4) {  // k_dyn_edges_rk1b_b's del4 term, same expressions
+    tue = ld2(p.tend_u_euler + o);  // PGF + del2, from k_dyn_edges_pgf_p
+    if (s.h_mom_eddy_visc4 > 0.0) {
+      const int2 veA = *reinterpret_cast<const int2*>(p.verticesOnEdge + 2 * eA);
+      const int2 veB = *reinterpret_cast<const int2*>(p.verticesOnEdge + 2 * eB);
+      const size_t ov1 = (size_t)sel(h, veA.x, veB.x) * K + 2 * lc, ov2 = (size_t)sel(h, veA.y, veB.y) * K + 2 * lc;
+      const d2 dd1 = ld2(p.delsq_divergence + o1), dd2 = ld2(p.delsq_divergence + o2);
+      const d2 dw1 = ld2(p.delsq_vorticity + ov1), dw2 = ld2(p.delsq_vorticity + ov2);
+      const double msd4 = sel(h, ld_uniform_f64(p.meshScalingDel4 + eA), ld_uniform_f64(p.meshScalingDel4 + eB));
+      const double invDv4 = sel(h, ld_uniform_f64(p.invDvEdge + eA), ld_uniform_f64(p.invDvEdge + eB));
+      const double u_mix_scale = msd4 * s.h_mom_eddy_visc4;
+      const double r_dc = u_mix_scale * cf.del4u_div_factor * invDc;
+      const double r_dv = u_mix_scale * fmin(invDv4, 4 * invDc);
+      tue.x = tue.x - re.x * ((dd2.x - dd1.x) * r_dc - (dw2.x - dw1.x) * r_dv);
+      tue.y = tue.y - re.y * ((dd2.y - dd1.y) * r_dc - (dw2.y - dw1.y) * r_dv);
+      if (solve) store(p.tend_u_euler, tue);
+    }
+  }
   if (finalize) {
     if (cf.rayleigh_damp_u) {
       const int k0 = K - cf.number_rayleigh_damp_u_levels;
@@ -2873,12 +2898,33 @@ __device__ __forceinline__ d2 ld_pp(const Dims& d, const Ptrs& p, const UnpackMa
   return ld2(fld + o);
 }
 
+// The averaging of ruAvg / wwAvg over the dynamics substeps (atm_rk_dynamics_substep_finish,
+// 6064-6078; k_substep_finish_v below) done where stage 3 of a dynamics substep stores them
+// (k_divdamp_p<true>, the recovery of k_acoustic_cells_r<ME, true>), on the value `a` still in
+// registers: the same sum and product, element for element.  srk3 asks for it (substep_avg_folded)
+// when nothing reads the stage's ruAvg / wwAvg before k_substep_finish_v would have run, and then
+// launches no k_substep_finish_v.  A substep that is not the last stores no ruAvg / wwAvg at all:
+// the next stage forms ruAvg afresh from dts * tend_u and sub-step 1 zeroes wwAvg.
+// sa: 0 = off (store `a` as before); else SA_ON | SA_FIRST for substep 1 | SA_LAST for the last one
+enum { SA_ON = 1, SA_FIRST = 2, SA_LAST = 4 };
+__device__ __forceinline__ void store_avg(double* avg, double* split, size_t i, double a, int sa, double inv) {
+  if (!sa) {
+    avg[i] = a;
+    return;
+  }
+  const double s = (sa & SA_FIRST) ? a : a + split[i];
+  split[i] = s;
+  if (sa & SA_LAST) avg[i] = s * inv;
+}
+
 // dl = 1: rtheta_pp_old holds rtheta_pp - rtheta_pp_old (k_acoustic_cells_r<ME, true> with dl)
 // rp: the stage's last damping also packs ru_p of the 876-887 exchange (XPack), or nothing
+// sa, sa_inv (REC only): the substep averaging of ruAvg on the recovered edges (store_avg)
 template <bool REC = false, bool UP = false, bool ODD = false>
 __global__ __launch_bounds__(PAIR_THREADS) void k_divdamp_p(Dims d, Ptrs p, double coef_divdamp, int phase, double dts,
                                                             int fresh, double invNs = 0.0, UnpackMap um = UnpackMap{},
-                                                            int dl = 0, XPack rp = XPack{}, XPack upk = XPack{}) {
+                                                            int dl = 0, XPack rp = XPack{}, XPack upk = XPack{},
+                                                            int sa = 0, double sa_inv = 0.0) {
   int eA, eB;
   bool hasB;
   if (!pair_edges(d, p, phase, eA, eB, hasB)) return;
@@ -2932,6 +2978,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_divdamp_p(Dims d, Ptrs p, doub
   const bool rB = onB && (phase ? bB : p.edge_bnd[eB]) == 0;
   const d2 rs = ld2(p.ru_save + o);
   const d2 ra = fresh ? ru : ld2(p.ruAvg + o);  // fresh: sub-step 1 left ruAvg = dts * tend_u
+  const d2 sp = (sa && !(sa & SA_FIRST)) ? ld2(p.ruAvg_split + o) : d2{0.0, 0.0};
   const d2 z1 = ld2(p.rho_zz2 + o1), z2 = ld2(p.rho_zz2 + o2);
   const d2 rr{rs.x + out.x, rs.y + out.y};
   const d2 un{2. * rr.x / (z1.x + z2.x), 2. * rr.y / (z1.y + z2.y)};
@@ -2941,7 +2988,14 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_divdamp_p(Dims d, Ptrs p, doub
     // edges k_recover_edges still recovers from it get it stored
     if (!(dl && (h ? rB : rA))) pst(p.ru_p + o, out, two);
     if (h ? rB : rA) {  // recover_edges (3048-3059), same expressions
-      pst(p.ruAvg + o, d2{rs.x + (ra.x * invNs), rs.y + (ra.y * invNs)}, two);
+      const d2 av{rs.x + (ra.x * invNs), rs.y + (ra.y * invNs)};
+      if (!sa) {
+        pst(p.ruAvg + o, av, two);
+      } else {  // store_avg on the pair
+        const d2 s2 = (sa & SA_FIRST) ? av : d2{av.x + sp.x, av.y + sp.y};
+        pst(p.ruAvg_split + o, s2, two);
+        if (sa & SA_LAST) pst(p.ruAvg + o, d2{s2.x * sa_inv, s2.y * sa_inv}, two);
+      }
       pst(p.ru + o, rr, two);
       pst(p.u2 + o, un, two);
     } else if (fresh) {
@@ -3383,7 +3437,7 @@ __device__ __forceinline__ RecIn load_rec_in(const Dims& d, const Ptrs& p, size_
 __device__ __forceinline__ void recover_cell_fused(const Dims& d, const Ptrs& p, int c, int k, double zz_k, double rws,
                                                    double fzm_k, double fzp_k, const RecIn& ri, double rhopp,
                                                    double rtpp, double rwp, double wwa, double dt, double invNs,
-                                                   int rk_step) {
+                                                   int rk_step, int sa, double sa_inv) {
   const int K = d.K;
   const size_t K1 = K + 1;
   const bool act = k < K;
@@ -3404,7 +3458,7 @@ __device__ __forceinline__ void recover_cell_fused(const Dims& d, const Ptrs& p,
   }
   double w = 0.0;  // w(1) = w(nVertLevels+1) = 0
   if (act && k >= 1) {
-    p.wwAvg[ow] = rws + (wwa * invNs);
+    store_avg(p.wwAvg, p.wwAvg_split, ow, rws + (wwa * invNs), sa, sa_inv);
     const double rw = rws + rwp;
     p.rw[ow] = rw;
     w = rw / (fzm * zz + fzp * zzm);  // divided by density in k_recover_cells3
@@ -3489,7 +3543,8 @@ __device__ __forceinline__ void load_ac_own(const Ptrs& p, size_t o, size_t ow, 
 template <int ME, bool FIN>
 __device__ __forceinline__ void acoustic_cells_col(const Dims& d, const Ptrs& p, int c, const AcIn<ME>& in, double dts,
                                                    int small_step, double epssm, double rdt, double invNs, int rk_step,
-                                                   int keep_pp, const PackMap& pk, int dl, const XPack& rp) {
+                                                   int keep_pp, const PackMap& pk, int dl, const XPack& rp, int sa = 0,
+                                                   double sa_inv = 0.0) {
   const int k = lane_id(), K = d.K;
   const bool act = k < K, actw = k <= K;
   const int kc = min(k, K - 1), kw = min(k, K);
@@ -3563,12 +3618,12 @@ __device__ __forceinline__ void acoustic_cells_col(const Dims& d, const Ptrs& p,
     if (actw) {
       if (!FIN || keep_pp) p.rw_p[ow] = rwp;
       if (!FIN) p.wwAvg[ow] = wwa;
-      else if (k == 0 || k == K) p.wwAvg[ow] = wwa;  // levels 2..K: recover_cell_fused
+      else if (k == 0 || k == K) store_avg(p.wwAvg, p.wwAvg_split, ow, wwa, sa, sa_inv);  // levels 2..K: recover_cell_fused
     }
     pack_column(pk, c, k, act, rt_new, rho_new);
     if (FIN) pack_rec_cell(rp, c, k, act, actw, rwp, rho_new, rt_new);
     if (FIN) ri = load_rec_in(d, p, o, rk_step);
-    if (FIN) recover_cell_fused(d, p, c, k, zz, rws, fzm, fzp, ri, rho_new, rt_new, rwp, wwa, rdt, invNs, rk_step);
+    if (FIN) recover_cell_fused(d, p, c, k, zz, rws, fzm, fzp, ri, rho_new, rt_new, rwp, wwa, rdt, invNs, rk_step, sa, sa_inv);
   } else {
     // specified zone (2710-2719): regional only, masks are 0 for global meshes
     if (act) {
@@ -3587,12 +3642,12 @@ __device__ __forceinline__ void acoustic_cells_col(const Dims& d, const Ptrs& p,
     if (actw) {
       p.rw_p[ow] = rwp;
       if (!FIN) p.wwAvg[ow] = wwa;
-      else if (k == 0 || k == K) p.wwAvg[ow] = wwa;
+      else if (k == 0 || k == K) store_avg(p.wwAvg, p.wwAvg_split, ow, wwa, sa, sa_inv);
     }
     pack_column(pk, c, k, act, rtpp, rhopp);
     if (FIN) pack_rec_cell(rp, c, k, act, actw, rwp, rhopp, rtpp);
     if (FIN) ri = load_rec_in(d, p, o, rk_step);
-    if (FIN) recover_cell_fused(d, p, c, k, zz, rws, fzm, fzp, ri, rhopp, rtpp, rwp, wwa, rdt, invNs, rk_step);
+    if (FIN) recover_cell_fused(d, p, c, k, zz, rws, fzm, fzp, ri, rhopp, rtpp, rwp, wwa, rdt, invNs, rk_step, sa, sa_inv);
   }
 }
 
@@ -3612,7 +3667,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) ACOUSTIC_CELLS_ATTR void k_acoustic_
                                                                     double epssm, double rdt = 0.0,
                                                                     double invNs = 0.0, int rk_step = 0,
                                                                     int keep_pp = 1, PackMap pk = PackMap{}, int dl = 0,
-                                                                    XPack rp = XPack{}) {
+                                                                    XPack rp = XPack{}, int sa = 0, double sa_inv = 0.0) {
   const int c = wave_elem(0);
   if (c >= d.nCells) return;
   const int k = lane_id(), K = d.K;
@@ -3661,7 +3716,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) ACOUSTIC_CELLS_ATTR void k_acoustic_
   // they name the buffers that hold these values until the recovery (srk3, stage_fin)
   in.rz = p.rho_zz2_rd[o], in.dss = p.dss[o], in.rws = p.rw_save[ow], in.rw = p.rw_rd[ow], in.w2 = p.w2_rd[ow];
   in.cofrz = p.cofrz[kc], in.rdzw = p.rdzw[kc], in.fzm = p.fzm[kc], in.fzp = p.fzp[kc];
-  acoustic_cells_col<ME, FIN>(d, p, c, in, dts, small_step, epssm, rdt, invNs, rk_step, keep_pp, pk, dl, rp);
+  acoustic_cells_col<ME, FIN>(d, p, c, in, dts, small_step, epssm, rdt, invNs, rk_step, keep_pp, pk, dl, rp, sa, sa_inv);
 }
 
 #ifndef MPAS_WIDE
@@ -3678,9 +3733,12 @@ __global__ __launch_bounds__(BLOCK_THREADS) ACOUSTIC_CELLS_ATTR void k_acoustic_
 // written here.
 // a.store_tend = 0: tend_w and tend_theta are not stored (the stage has no second sub-step to read
 // them and is not the dt's last, whose values the pool keeps)
+// sa, sa_inv: the substep averaging of wwAvg in the fused recovery (store_avg), FIN forms only
 struct TendAcArgs {
   double dts, epssm, rdt, invNs;
   int rk_step, keep_pp, dl, store_tend;
+  int sa;
+  double sa_inv;
 };
 template <int ME, bool RK1, bool FIN>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_acoustic_r(Dims d, Ptrs p, Config cf, DynTendScal s,
@@ -3722,7 +3780,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_acoustic_r(Dims d,
   in.zz = cy.zz, in.rz = cy.rz, in.rws = cy.rws, in.rw = cy.rw, in.w2 = cy.w2;
   in.rdzw = cy.rdzw, in.fzm = cy.fzm, in.fzp = cy.fzp;
   acoustic_cells_col<ME, FIN>(d, p, c, in, a.dts, 1, a.epssm, a.rdt, a.invNs, a.rk_step, a.keep_pp, PackMap{}, a.dl,
-                              XPack{});
+                              XPack{}, a.sa, a.sa_inv);
 }
 #endif
 
@@ -4129,9 +4187,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_diag_edges(Dims d, Ptrs p, co
 // this kernel already gathers -- k_dyn_cells1 at rk_step 2 / 3 computes nothing else, and no
 // kernel in between reads or writes ru or h_divergence; srk3 then skips that launch.
 template <int ME>
-__global__ __launch_bounds__(BLOCK_THREADS) void k_recover_cells3_b(Dims d, Ptrs p, int phase, int hdiv) {
-  const int c = wave_elem(0);
-  if (c >= d.nCells) return;
+__device__ __forceinline__ void recover_cells3_col(const Dims& d, const Ptrs& p, int c, int phase, int hdiv) {
   if (p.bdyMaskCell[c] > N_RELAX_ZONE) return;  // no specified-zone update (3069; any run)
   const int k = lane_id(), K = d.K;
   const size_t K1 = K + 1;
@@ -4185,12 +4241,16 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_recover_cells3_b(Dims d, Ptrs
   else if (act) w = w / (fzm * rz + fzp * rzm);
   if (act) p.w2[ow] = w;  // w(K+1) stays 0
 }
-
 template <int ME>
-__global__ __launch_bounds__(BLOCK_THREADS) void k_diag_cells_b(Dims d, Ptrs p, const double* __restrict__ u,
-                                                                double apvm, int store_dv = 1) {
+__global__ __launch_bounds__(BLOCK_THREADS) void k_recover_cells3_b(Dims d, Ptrs p, int phase, int hdiv) {
   const int c = wave_elem(0);
   if (c >= d.nCells) return;
+  recover_cells3_col<ME>(d, p, c, phase, hdiv);
+}
+
+template <int ME>
+__device__ __forceinline__ void diag_cells_col(const Dims& d, const Ptrs& p, int c, const double* __restrict__ u,
+                                               double apvm, int store_dv) {
   const int k = lane_id(), K = d.K;
   if (k >= K) return;
   const int ne = p.nEdgesOnCell[c];
@@ -4241,6 +4301,31 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_diag_cells_b(Dims d, Ptrs p, 
   p.ke[o] = ke;
   if (apvm > 0.0) p.pv_cell[o] = pvc;
 }
+template <int ME>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_diag_cells_b(Dims d, Ptrs p, const double* __restrict__ u,
+                                                                double apvm, int store_dv = 1) {
+  const int c = wave_elem(0);
+  if (c >= d.nCells) return;
+  diag_cells_col<ME>(d, p, c, u, apvm, store_dv);
+}
+#ifndef MPAS_WIDE
+// The w recovery (k_recover_cells3_b, phase 0) and the diagnostics' cell kernel (k_diag_cells_b) of
+// column c in one launch, after k_diag_vertices_p: srk3 runs them back to back when nothing lies
+// between them (one block without exchanges or LBCs, transport outside the dynamics), and
+// k_diag_vertices_p reads nothing the recovery writes (w, h_divergence).  The two bodies share
+// only the cell's index row, so no stream is saved: both are latency-bound one-wavefront-per-column
+// kernels, and the launch saves one kernel's tail per call.  Same device functions
+// as the two kernels, so the bits are theirs.
+template <int ME>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_recover3_diag_cells_b(Dims d, Ptrs p, int hdiv,
+                                                                         const double* __restrict__ u, double apvm,
+                                                                         int store_dv) {
+  const int c = wave_elem(0);
+  if (c >= d.nCells) return;
+  recover_cells3_col<ME>(d, p, c, 0, hdiv);
+  diag_cells_col<ME>(d, p, c, u, apvm, store_dv);
+}
+#endif
 
 template <int NE2>
 __global__ __launch_bounds__(EDGE_THREADS) void k_diag_edges_b(Dims d, Ptrs p, const double* __restrict__ u,

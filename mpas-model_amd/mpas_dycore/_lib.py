@@ -29,7 +29,7 @@ EXPORTS = (
     "mpas_dyc_last_exchange", "mpas_dyc_rccl_version", "mpas_dyc_model_init", "mpas_dyc_set_exchange_positions",
     "mpas_dyc_init_deriv_two", "mpas_dyc_init_zb", "mpas_dyc_init_reconstruct", "mpas_dyc_comm_check",
     "mpas_dyc_fused_tend_acoustic", "mpas_dyc_set_iau", "mpas_dyc_iau_weight", "mpas_dyc_set_diag_update",
-    "mpas_dyc_diag_update", "mpas_dyc_diag_reset",
+    "mpas_dyc_diag_update", "mpas_dyc_diag_reset", "mpas_dyc_folded_passes",
 )
 HOST_ONLY = -2  # MPAS_DYC_HOST_ONLY: planner-only context
 PRINT_GLOBAL_MINMAX_VEL, PRINT_DETAILED_MINMAX_VEL, PRINT_GLOBAL_MINMAX_SCA = 1, 2, 4
@@ -169,6 +169,7 @@ def load() -> C.CDLL:
     lib.mpas_dyc_graph_active.argtypes = [vp]
     lib.mpas_dyc_block_layout.argtypes = [vp, i32, C.POINTER(i32)]
     lib.mpas_dyc_fused_tend_acoustic.argtypes = [vp]
+    lib.mpas_dyc_folded_passes.argtypes = [vp]
     lib.mpas_dyc_set_profile.argtypes = [vp, i32]
     lib.mpas_dyc_get_profile.argtypes = [vp, C.POINTER(dbl), i32]
     lib.mpas_dyc_last_exchange.argtypes = [vp]

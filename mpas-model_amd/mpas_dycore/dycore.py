@@ -533,6 +533,17 @@ class Dycore:
         m = int(self.lib.mpas_dyc_fused_tend_acoustic(self.h))
         return tuple(rk for rk in (1, 2, 3) if m & (1 << (rk - 1)))
 
+    def folded_passes(self) -> tuple:
+        """The passes this context folds into the kernels that produce their inputs
+        (mpas_dyc_folded_passes): "substep_avg" -- stage 3's last damping and cell phase average
+        ruAvg / wwAvg over the dynamics substeps and k_substep_finish_v is not launched
+        (MPAS_DYCORE_FOLD_SUBSTEP_AVG=0: off); "rk1_edges" -- stage 1's edge kernel applies the del4
+        term and forms the final tend_u and k_dyn_edges_rk1b_b is not launched
+        (MPAS_DYCORE_FOLD_RK1_EDGES=0: off); "recover_diag" -- the w recovery runs in the launch of the
+        diagnostics' cell kernel (MPAS_DYCORE_FUSE_RECOVER_DIAG=0: off).  () when none applies."""
+        m = int(self.lib.mpas_dyc_folded_passes(self.h))
+        return tuple(n for i, n in enumerate(("substep_avg", "rk1_edges", "recover_diag")) if m & (1 << i))
+
     def exchange_profile(self, dt: float, itimestep: int = 1) -> dict:
         """One eager atm_timestep with HIP events around every exchange's exposed part and every
         RCCL group (mpas_dyc_set_profile / mpas_dyc_get_profile); synchronous.  Shift the time
