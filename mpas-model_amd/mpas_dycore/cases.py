@@ -105,7 +105,60 @@ def varres_case(ncells: int, ratio: float = 20.0, K: int = 56, ns: int = 1, mois
     return case
 
 
-def regional_lbc(case: dict, interior_deg: float = 40.0, interval_end: float = 10800.0) -> tuple[dict, dict]:
+STRESS_DT = 2880.0
+
+
+def stress_case(K: int, ns: int = 3, **config) -> dict:
+    """The moist JW state on x1.642 with tracers and a mixing coefficient that load the paths the
+    smooth case barely takes.  config_smagorinsky_coef = 1 puts most of kdiff at its cap
+    (0.01 len_disp^2 / dt); the tracer species are discontinuous, so the monotone limiter rescales
+    fluxes by factors well below 1 and the unlimited scheme undershoots zero:
+      species 1 (and 3, ns = 6): a top-hat, 1e-3 (5e-4) within 0.6 rad of (1, 0, 0) ((0, 1, 0)) on
+        the levels (3K)//20 .. (11K)//20, exactly 0 elsewhere;
+      species 2 (and 4): 1e-3 r1 (r2 > 0.5), r1 and r2 uniform noise (seed 7, 8): half the entries 0;
+      species 5: identically 0.
+    qv (species 0) stays the JW moisture.  ``config`` overrides namelist options; it goes through
+    build_case, since model_init folds config_coef_3rd_order into adv_coefs_3rd and zb3_cell.
+    Meant to run with moist_end = ns and dt = case["dt"] = 2880 s, the step the x1.642 parity tests
+    take (half of jw_dt(3); the step is an argument of atm_timestep, config_dt is not read)."""
+    if ns not in (3, 6):
+        raise ValueError(f"stress_case: ns = {ns}, the species are defined for 3 and 6")
+    level = 3
+    m = _mesh(level, 20)
+    cfg = dict(config_len_disp=jw_len_disp(level), config_dt=jw_dt(level), config_time_integration_order=2,
+               config_smagorinsky_coef=1.0)
+    cfg.update(config)
+    case = build_case(m, K=K, ns=ns, moist=True, config=cfg)
+    case["dt"] = STRESS_DT
+    nC = case["nCells"]
+    shape = np.asarray(case["scalars"]).shape
+    sc = np.array(case["scalars"], dtype=np.float64).reshape(nC, K, ns)
+    xyz = np.stack([np.asarray(case["xCell"]), np.asarray(case["yCell"]), np.asarray(case["zCell"])], 1)
+    xyz = xyz / np.sqrt((xyz ** 2).sum(1))[:, None]
+    kk = np.arange(K)
+    levels = (kk >= (3 * K) // 20) & (kk <= (11 * K) // 20)
+
+    def top_hat(centre, amplitude):
+        ang = np.arccos(np.clip(xyz @ np.asarray(centre, dtype=np.float64), -1.0, 1.0))
+        return np.where((ang < 0.6)[:, None] & levels[None, :], amplitude, 0.0)
+
+    def noise(seed):
+        rng = np.random.default_rng(seed)
+        r1 = rng.random((nC, K))
+        r2 = rng.random((nC, K))
+        return 1e-3 * r1 * (r2 > 0.5)
+
+    sc[:, :, 1] = top_hat((1.0, 0.0, 0.0), 1e-3)
+    sc[:, :, 2] = noise(7)
+    if ns == 6:
+        sc[:, :, 3] = top_hat((0.0, 1.0, 0.0), 5e-4)
+        sc[:, :, 4] = noise(8)
+        sc[:, :, 5] = 0.0
+    case["scalars"] = sc.reshape(shape)
+    return case
+
+
+def regional_lbc(case: dict,interior_deg: float = 40.0, interval_end: float = 10800.0) -> tuple[dict, dict]:
     """A limited-area configuration on a global case (config_apply_lbcs): the cells farther than
     ``interior_deg`` from (0N, 0E) form the boundary zones, ring by ring outward -- bdyMaskCell 1..5
     relaxation, 6 and 7 (and everything beyond) specified -- as a regional mesh's masks count them
