@@ -93,7 +93,8 @@ const char* mpas_dyc_last_error(const mpas_dyc_ctx* ctx);
 /* Host <-> device copy of one named pool field (pool: "mesh","state","diag","tend",
  * "tend_physics", "lbc", "tend_iau" -- see mpas_dyc_set_iau; scalars 0-d fields cf1/cf2/cf3 take 8
  * bytes). nbytes must match.  diag.w_velocity_max / wind_speed_level1_max / updraft_helicity_max: see
- * mpas_dyc_set_diag_update. */
+ * mpas_dyc_set_diag_update.  "diag_physics" rainnc / rainncv / precipw / i_rainnc, diag.surface_pressure,
+ * tend.tend_sfc_pressure: see mpas_dyc_set_microphysics. */
 int mpas_dyc_set_field(mpas_dyc_ctx* ctx, const char* pool, const char* name, int32_t time_level,
                        const void* host, int64_t nbytes);
 int mpas_dyc_get_field(mpas_dyc_ctx* ctx, const char* pool, const char* name, int32_t time_level,
@@ -244,6 +245,44 @@ int mpas_dyc_diag_update(mpas_dyc_ctx* ctx);
  * update mask is.  Asynchronous.  Unknown bits: MPAS_DYC_EINVAL; fields never allocated: nothing to
  * do; MPAS_DYC_HOST_ONLY: MPAS_DYC_ESTATE. */
 int mpas_dyc_diag_reset(mpas_dyc_ctx* ctx, int32_t flags);
+/* The cloud microphysics call of atm_srk3 (mpas_atm_time_integration.F:1650-1660) on the device, for
+ * config_microp_scheme = 'mp_kessler': everything driver_microphysics does for that scheme --
+ * precip_from_MPAS, microphysics_from_MPAS, kessler (physics_wrf/module_mp_kessler.F, dt_microp = dt,
+ * n_microp = 1), precip_to_MPAS, microphysics_to_MPAS (mpas_atmphys_interface.F:473-785,
+ * mpas_atmphys_driver_microphysics.F:429-583) -- on the cells 1..nCellsSolve of every block, one kernel
+ * launch per block (kessler.hip), fp64 in the Fortran's operand order.  It updates, on the given time
+ * level, state.theta_m and the scalars index_qv / index_qc / index_qr, and diag.rtheta_p, exner,
+ * pressure_p, tend.rt_diabatic_tend, and the fields
+ *   diag_physics.rainnc, rainncv, precipw (fp64) and i_rainnc (int32), diag.surface_pressure,
+ *   tend.tend_sfc_pressure, each (nCells+1);
+ * these are allocated, zeroed, at the first mpas_dyc_set_field of one of them or when the switch goes on
+ * -- a context that asks for neither holds none of them (mpas_dyc_field_bytes returns 0) and behaves as
+ * before -- and set_field / get_field / field_bytes / field_device_ptr work on them from then on (a
+ * restart puts rainnc, i_rainnc and surface_pressure back with set_field).  Halo cells and the garbage
+ * slot keep what they hold: the step's first exchange refreshes theta_m, scalars, rtheta_p, exner and
+ * pressure_p there.  Not part of it: the l_diags branch (compute_relhum); Thompson and WSM6 stay with
+ * the host (MPAS_DYC_PHYSICS_MICROPHYSICS).
+ * mpas_dyc_set_microphysics(scheme, index_qc, index_qr, bucket_rainnc): with MPAS_DYC_MICROP_KESSLER,
+ * every mpas_dyc_timestep runs the scheme on time level 2 after the negative-scalar clip (1645-1646)
+ * and before the end of the step (the regional reset, summarize_timestep), captured with the step (the
+ * sedimentation's data-dependent split loop is inside the kernel).  index_qc / index_qr are the 1-based
+ * scalar indices of cloud and rain water (index_qv is the context's); bucket_rainnc =
+ * config_bucket_rainnc (> 0: rainnc above it moves one bucket into i_rainnc).  While on it implies the
+ * step of MPAS_DYC_PHYSICS_TENDENCIES, as mpas_dyc_set_iau does and for the same reason (the call sits
+ * inside the reference's DO_PHYSICS block), and the step reads tend.rt_diabatic_tend.  Changing the
+ * switch drops the captured steps.  MPAS_DYC_EINVAL: an unknown scheme, an index outside
+ * 1..num_scalars, two of index_qv / index_qc / index_qr equal; MPAS_DYC_ESTATE: together with
+ * MPAS_DYC_PHYSICS_MICROPHYSICS (the host's microphysics), in whichever order the two are set.  On a
+ * MPAS_DYC_HOST_ONLY context the switch is kept and nothing is allocated. */
+#define MPAS_DYC_MICROP_OFF 0
+#define MPAS_DYC_MICROP_KESSLER 1
+int mpas_dyc_set_microphysics(mpas_dyc_ctx* ctx, int32_t scheme, int32_t index_qc, int32_t index_qr,
+                              double bucket_rainnc);
+/* The same call eager and on its own, for tests and hosts that sequence the step themselves: the
+ * scheme set by mpas_dyc_set_microphysics (MPAS_DYC_ESTATE if off, or on a MPAS_DYC_HOST_ONLY context)
+ * with dt_microp = dt on time_level (1 or 2).  Asynchronous on the compute stream (synchronous only
+ * while mpas_dyc_set_profile is on, which times it: mpas_dyc_get_profile out[7]). */
+int mpas_dyc_microphysics(mpas_dyc_ctx* ctx, double dt, int32_t time_level);
 /* Regional lateral boundary conditions, config_apply_lbcs (mpas_atm_time_integration.F:683-778,
  * 934-987, 1109-1180, 1253-1270, 1491-1560, 1672-1790; the routines at 6088-6671).  apply = 1 turns
  * them on (the pair kernel layout is required).  The host sets, as in the reference's lbc pool
@@ -505,7 +544,8 @@ double mpas_dyc_acoustic_bytes(const mpas_dyc_ctx* ctx);
  * out[5] (profile on or off) = steps captured into a hipGraph since the context was created: it
  * stays put while steps replay (one capture per buffer layout and IAU branch, mpas_dyc_set_iau).
  * out[6] = ms of the last mpas_dyc_diag_update called with the profile on (HIP events around its
- * launches on the compute stream; that call is synchronous). */
+ * launches on the compute stream; that call is synchronous).
+ * out[7] = the same for the last mpas_dyc_microphysics called with the profile on. */
 int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on);
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n);
 /* The plan key of the exchange whose RCCL group was enqueued last ("warm_rccl <key>" while the

@@ -33,6 +33,7 @@
 #include "model_init.hip"
 #include "iau.hip"
 #include "convdiag.hip"
+#include "kessler.hip"
 
 using namespace mpas;
 
@@ -282,6 +283,15 @@ struct mpas_dyc_ctx {
   int diag_flags = 0;
   bool diag_alloc = false;
   double diag_ms = 0.0;                 // the last mpas_dyc_diag_update under mpas_dyc_set_profile (out[6])
+  // the device microphysics (mpas_dyc_set_microphysics; kessler.hip): the MPAS_DYC_MICROP_* scheme of
+  // the step, the 0-based scalar indices of cloud and rain water, config_bucket_rainnc, and whether
+  // diag_physics.rainnc / rainncv / precipw / i_rainnc, diag.surface_pressure and
+  // tend.tend_sfc_pressure are allocated (when the switch first goes on, or at a set_field of one of them)
+  int microp = 0;
+  int mp_iqc = -1, mp_iqr = -1;
+  double mp_bucket = 0.0;
+  bool mp_alloc = false;
+  double microp_ms = 0.0;               // the last mpas_dyc_microphysics under mpas_dyc_set_profile (out[7])
   bool tail_pending = false;            // MPAS_DYC_PHYSICS_MICROPHYSICS: a step ran, mpas_dyc_finish_step not yet
   // exchange profile (mpas_dyc_set_profile): eager steps with HIP events around the exposed part of
   // every exchange (a blocking exchange whole; a split-phase one from the compute stream reaching
@@ -361,6 +371,11 @@ bool is_convdiag(const Field& f) {
   for (const char* n : CONVDIAG_FIELDS)
     if (f.name == n) return true;
   return false;
+}
+// the fields only the device microphysics touches (mpas_dyc_set_microphysics)
+bool is_microp(const Field& f) {
+  if (f.pool == "diag_physics") return true;
+  return (f.pool == "diag" && f.name == "surface_pressure") || (f.pool == "tend" && f.name == "tend_sfc_pressure");
 }
 // The Registry.xml var_structs the dycore touches (same list the oracle harness builds).
 void build_registry(Block& c) {
@@ -532,6 +547,15 @@ void build_registry(Block& c) {
     add(c, "diag", n, L_CELL, 1);
     c.fields.back().lazy = true;
   }
+  // the device microphysics' own fields (Registry.xml diag_physics / diag / tend: (nCells + 1) each):
+  // allocated, zeroed, at the first set_field of one of them or when mpas_dyc_set_microphysics turns
+  // a scheme on (microp_alloc)
+  for (const char* n : {"rainnc", "rainncv", "precipw"}) add(c, "diag_physics", n, L_CELL, 1);
+  add(c, "diag_physics", "i_rainnc", L_CELL, 1, 1, true);
+  add(c, "diag", "surface_pressure", L_CELL, 1);
+  add(c, "tend", "tend_sfc_pressure", L_CELL, 1);
+  for (auto& f : c.fields)
+    if (is_microp(f)) f.lazy = true;
   // the maxEdges- and maxEdges2-strided mesh arrays (pack_mesh)
   for (const char* n : {"edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "coeffs_reconstruct",
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
@@ -563,7 +587,10 @@ T* P(mpas_dyc_ctx* c, Block& b, const char* pool, const char* name, int tl = 1) 
 }
 
 // DO_PHYSICS coupling of the step: the host's flag, or implied by the incremental analysis update
-bool physics_tendencies(const mpas_dyc_ctx* c) { return (c->physics & MPAS_DYC_PHYSICS_TENDENCIES) || c->iau_on; }
+// or by the device microphysics
+bool physics_tendencies(const mpas_dyc_ctx* c) {
+  return (c->physics & MPAS_DYC_PHYSICS_TENDENCIES) || c->iau_on || c->microp;
+}
 // the step being enqueued applies the IAU forcing (mpas_atm_iau.F:118)
 bool iau_active(const mpas_dyc_ctx* c) { return c->iau_on && c->iau_wgt > 1.0e-12; }
 // Ptrs::tend_*_physics are the library's sums (scratch.iau_*): in a forced step, and in every step of
@@ -755,6 +782,58 @@ int convdiag_alloc(mpas_dyc_ctx* ctx) {
     }
   HIPCHK(hipStreamSynchronize(ctx->stream));  // and before a set_field / get_field of the caller
   ctx->diag_alloc = true;
+  return MPAS_DYC_OK;
+}
+
+// the device microphysics' fields of every block, zeroed
+int microp_alloc(mpas_dyc_ctx* ctx) {
+  for (auto& b : ctx->blk)
+    for (auto& f : b.fields) {
+      if (f.buf[0] || !is_microp(f)) continue;
+      const int64_t nb = field_bytes(b, f) + 256;
+      HIPCHK(hipMalloc(&f.buf[0], nb));
+      HIPCHK(hipMemsetAsync(f.buf[0], 0, nb, ctx->stream));
+    }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->mp_alloc = true;
+  return MPAS_DYC_OK;
+}
+
+// driver_microphysics for mp_kessler on time level tl of every block: one launch per block
+int kessler_enqueue(mpas_dyc_ctx* ctx, double dt, int tl) {
+  if (ctx->planning) return MPAS_DYC_OK;
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    if (d.nCellsSolve <= 0) continue;
+    Kessler a{};
+    a.nCellsSolve = d.nCellsSolve, a.nCells = d.nCells, a.K = d.K;
+    a.iqv = ctx->index_qv, a.iqc = ctx->mp_iqc, a.iqr = ctx->mp_iqr;
+    a.dt = dt, a.bucket = ctx->mp_bucket;
+    a.zz = P<const double>(ctx, b, "mesh", "zz");
+    a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
+    a.rho_zz = P<const double>(ctx, b, "state", "rho_zz", tl);
+    a.rtheta_base = P<const double>(ctx, b, "diag", "rtheta_base");
+    a.exner_base = P<const double>(ctx, b, "diag", "exner_base");
+    a.pressure_base = P<const double>(ctx, b, "diag", "pressure_base");
+    a.theta_m = P<double>(ctx, b, "state", "theta_m", tl);
+    a.scalars = P<double>(ctx, b, "state", "scalars", tl);
+    a.exner = P<double>(ctx, b, "diag", "exner");
+    a.rtheta_p = P<double>(ctx, b, "diag", "rtheta_p");
+    a.pressure_p = P<double>(ctx, b, "diag", "pressure_p");
+    a.rt_diabatic_tend = P<double>(ctx, b, "tend", "rt_diabatic_tend");
+    a.rainnc = P<double>(ctx, b, "diag_physics", "rainnc");
+    a.rainncv = P<double>(ctx, b, "diag_physics", "rainncv");
+    a.precipw = P<double>(ctx, b, "diag_physics", "precipw");
+    a.i_rainnc = P<int>(ctx, b, "diag_physics", "i_rainnc");
+    a.surface_pressure = P<double>(ctx, b, "diag", "surface_pressure");
+    a.tend_sfc_pressure = P<double>(ctx, b, "tend", "tend_sfc_pressure");
+    if (d.K > 64 * KESSLER_CHUNKS) {
+      ctx->err = "the Kessler kernel of this build holds at most " + std::to_string(64 * KESSLER_CHUNKS) + " levels";
+      return MPAS_DYC_EINVAL;
+    }
+    hipLaunchKernelGGL(k_kessler<KESSLER_CHUNKS>, dim3((unsigned)((d.nCellsSolve + KESSLER_WAVES - 1) / KESSLER_WAVES)),
+                       dim3(KESSLER_THREADS), 0, ctx->stream, a);
+  }
   return MPAS_DYC_OK;
 }
 
@@ -2103,6 +2182,8 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
         hipLaunchKernelGGL(k_physics_clip_scalars, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)),
                            dim3(256), 0, ctx->stream, ::P<double>(ctx, b, "state", "scalars", 2), n);
     }
+    // 1650-1660: driver_microphysics on time level 2, when the device owns it (mpas_dyc_set_microphysics)
+    if (ctx->microp == MPAS_DYC_MICROP_KESSLER) CHK(kessler_enqueue(ctx, dt, 2));
   }
   // the rest of the step follows the microphysics (1650-1660): when the host runs it, the host
   // calls mpas_dyc_finish_step after it
@@ -2509,7 +2590,9 @@ int64_t mpas_dyc_block_field_bytes(const mpas_dyc_ctx* ctx, int32_t block, const
   const Block& b = ctx->blk[block];
   auto it = b.by_name.find(std::string(pool) + "." + name);
   if (it == b.by_name.end()) return 0;
-  return field_bytes(b, b.fields[it->second]);
+  const Field& f = b.fields[it->second];
+  if (is_microp(f) && !f.buf[0]) return 0;  // held only by a context that asked for them
+  return field_bytes(b, f);
 }
 
 int64_t mpas_dyc_field_bytes(const mpas_dyc_ctx* ctx, const char* pool, const char* name) {
@@ -2565,6 +2648,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
   const int slot = slot_of(ctx, *f, time_level);
   HIPCHK(hipSetDevice(ctx->device));
   if (f->lazy && !f->buf[slot] && is_convdiag(*f)) CHK(convdiag_alloc(ctx));  // all three, zeroed
+  if (f->lazy && !f->buf[slot] && is_microp(*f)) CHK(microp_alloc(ctx));      // all six, zeroed
   if (f->lazy && !f->buf[slot]) {
     HIPCHK(hipMalloc(&f->buf[slot], nb + 256));
     if (f->pool == "tend_iau") {  // the pool is whole once one field is set: the others are zero until set
@@ -2631,7 +2715,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
       const double* h = (const double*)host;
       int nz = 0;
       for (int64_t i = 0; i < nb / 8 && !nz; ++i) nz = h[i] != 0.0;
-      b.d.diabatic = nz;
+      b.d.diabatic = nz || ctx->microp;  // the device microphysics writes it every step
     }
   }
   return MPAS_DYC_OK;
@@ -3062,6 +3146,10 @@ int mpas_dyc_set_physics(mpas_dyc_ctx* ctx, int32_t flags) {
     return MPAS_DYC_EINVAL;
   if (ctx->host_only) return MPAS_DYC_ESTATE;
   if ((flags & MPAS_DYC_PHYSICS_RQVDYNTEN) && !(flags & MPAS_DYC_PHYSICS_TENDENCIES)) return MPAS_DYC_EINVAL;
+  if ((flags & MPAS_DYC_PHYSICS_MICROPHYSICS) && ctx->microp) {
+    ctx->err = "MPAS_DYC_PHYSICS_MICROPHYSICS (the host's microphysics) with mpas_dyc_set_microphysics on";
+    return MPAS_DYC_ESTATE;
+  }
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->physics = flags;
@@ -3167,6 +3255,77 @@ int mpas_dyc_diag_update(mpas_dyc_ctx* ctx) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
     (void)hipEventElapsedTime(&t, ctx->prof_step[0], ctx->prof_step[1]);
     ctx->diag_ms = t;
+  }
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_set_microphysics(mpas_dyc_ctx* ctx, int32_t scheme, int32_t index_qc, int32_t index_qr,
+                              double bucket_rainnc) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (scheme != MPAS_DYC_MICROP_OFF && scheme != MPAS_DYC_MICROP_KESSLER) {
+    ctx->err = "mpas_dyc_set_microphysics: unknown scheme";
+    return MPAS_DYC_EINVAL;
+  }
+  if (scheme != MPAS_DYC_MICROP_OFF) {
+    const int ns = ctx->blk.empty() ? 0 : ctx->blk[0].d.ns;
+    if (index_qc < 1 || index_qc > ns || index_qr < 1 || index_qr > ns || index_qc == index_qr ||
+        index_qc - 1 == ctx->index_qv || index_qr - 1 == ctx->index_qv) {
+      ctx->err = "mpas_dyc_set_microphysics: index_qc / index_qr must be distinct scalars in 1..num_scalars, not index_qv";
+      return MPAS_DYC_EINVAL;
+    }
+    if (ctx->physics & MPAS_DYC_PHYSICS_MICROPHYSICS) {
+      ctx->err = "mpas_dyc_set_microphysics with MPAS_DYC_PHYSICS_MICROPHYSICS (the host's microphysics) set";
+      return MPAS_DYC_ESTATE;
+    }
+    for (auto& b : ctx->blk)
+      if (b.d.K > 64 * KESSLER_CHUNKS) {
+        ctx->err = "the Kessler kernel of this build holds at most " + std::to_string(64 * KESSLER_CHUNKS) + " levels";
+        return MPAS_DYC_EINVAL;
+      }
+  }
+  if (!ctx->host_only) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (scheme != MPAS_DYC_MICROP_OFF && !ctx->mp_alloc) CHK(microp_alloc(ctx));
+  }
+  ctx->microp = scheme;
+  if (scheme != MPAS_DYC_MICROP_OFF) {
+    ctx->mp_iqc = index_qc - 1;
+    ctx->mp_iqr = index_qr - 1;
+    ctx->mp_bucket = bucket_rainnc;
+  }
+  for (auto& b : ctx->blk) {
+    b.d.physics = physics_tendencies(ctx) ? 1 : 0;
+    if (scheme != MPAS_DYC_MICROP_OFF) b.d.diabatic = 1;  // the step reads the scheme's rt_diabatic_tend
+  }
+  if (!ctx->host_only) drop_graphs(ctx);  // captured steps bake the switch, the indices and the bucket in
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_microphysics(mpas_dyc_ctx* ctx, double dt, int32_t time_level) {
+  if (!ctx || !(dt > 0.0) || (time_level != 1 && time_level != 2)) return MPAS_DYC_EINVAL;
+  if (ctx->host_only) {
+    ctx->err = "host-only context holds no fields";
+    return MPAS_DYC_ESTATE;
+  }
+  if (ctx->microp == MPAS_DYC_MICROP_OFF) {
+    ctx->err = "mpas_dyc_microphysics: no scheme set (mpas_dyc_set_microphysics)";
+    return MPAS_DYC_ESTATE;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (ctx->profile) {
+    for (auto& e : ctx->prof_step)
+      if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(ctx->prof_step[0], ctx->stream));
+  }
+  CHK(kessler_enqueue(ctx, dt, time_level));
+  HIPCHK(hipGetLastError());
+  if (ctx->profile) {  // measurement: synchronous, the launches between two events
+    float t = 0.f;
+    HIPCHK(hipEventRecord(ctx->prof_step[1], ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    (void)hipEventElapsedTime(&t, ctx->prof_step[0], ctx->prof_step[1]);
+    ctx->microp_ms = t;
   }
   return MPAS_DYC_OK;
 }
@@ -3559,7 +3718,7 @@ int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on) {
 
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n) {
   if (!ctx || !out || n < 1) return MPAS_DYC_EINVAL;
-  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->diag_ms : 0.0;
+  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->diag_ms : i == 7 ? ctx->microp_ms : 0.0;
   return MPAS_DYC_OK;
 }
 

@@ -29,12 +29,15 @@ EXPORTS = (
     "mpas_dyc_last_exchange", "mpas_dyc_rccl_version", "mpas_dyc_model_init", "mpas_dyc_set_exchange_positions",
     "mpas_dyc_init_deriv_two", "mpas_dyc_init_zb", "mpas_dyc_init_reconstruct", "mpas_dyc_comm_check",
     "mpas_dyc_fused_tend_acoustic", "mpas_dyc_set_iau", "mpas_dyc_iau_weight", "mpas_dyc_set_diag_update",
-    "mpas_dyc_diag_update", "mpas_dyc_diag_reset", "mpas_dyc_folded_passes",
+    "mpas_dyc_diag_update", "mpas_dyc_diag_reset", "mpas_dyc_folded_passes", "mpas_dyc_set_microphysics",
+    "mpas_dyc_microphysics",
 )
 HOST_ONLY = -2  # MPAS_DYC_HOST_ONLY: planner-only context
 PRINT_GLOBAL_MINMAX_VEL, PRINT_DETAILED_MINMAX_VEL, PRINT_GLOBAL_MINMAX_SCA = 1, 2, 4
 # MPAS_DYC_DIAG_*: the running maxima of mpas_dyc_diag_update
 DIAG_W_VELOCITY_MAX, DIAG_WIND_SPEED_LEVEL1_MAX, DIAG_UPDRAFT_HELICITY_MAX = 1, 2, 4
+# MPAS_DYC_MICROP_*: the scheme of mpas_dyc_set_microphysics
+MICROP_OFF, MICROP_KESSLER = 0, 1
 CELL, EDGE, VERTEX = 0, 1, 2
 SEND, RECV = 0, 1
 
@@ -135,6 +138,8 @@ def load() -> C.CDLL:
     lib.mpas_dyc_set_diag_update.argtypes = [vp, i32]
     lib.mpas_dyc_diag_update.argtypes = [vp]
     lib.mpas_dyc_diag_reset.argtypes = [vp, i32]
+    lib.mpas_dyc_set_microphysics.argtypes = [vp, i32, i32, i32, dbl]
+    lib.mpas_dyc_microphysics.argtypes = [vp, dbl, i32]
     lib.mpas_dyc_time_acoustic_step.argtypes = [vp, dbl, i32, i32, C.POINTER(dbl), C.POINTER(dbl)]
     lib.mpas_dyc_use_graph.argtypes = [vp, i32]
     lib.mpas_dyc_acoustic_bytes.argtypes = [vp]

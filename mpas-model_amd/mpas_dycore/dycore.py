@@ -36,7 +36,8 @@ _SKIP = set(STATE_INPUTS) | set(DIAG_INPUTS) | {"xCell", "yCell", "zCell", "xEdg
                                                 "yVertex", "zVertex",
                                                 "latVertex", "lonVertex", "areaCell", "areaTriangle",
                                                 "meshDensity", "indexToCellID", "deriv_two", "zb", "zb3",
-                                                "w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max"}
+                                                "w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max",
+                                                *F.MICROP_FIELD}
 
 
 def _host_allgather_fn(group, nranks: int):
@@ -280,7 +281,7 @@ class Dycore:
         nb = self.lib.mpas_dyc_block_field_bytes(self.h, block, pool.encode(), name.encode())
         if nb <= 0:
             raise DycoreError(f"unknown field {pool}.{name}")
-        buf = np.empty(nb // 8, dtype=np.float64)
+        buf = np.empty(nb // 4, dtype=np.int32) if name in F.INT_FIELDS else np.empty(nb // 8, dtype=np.float64)
         self._check(self.lib.mpas_dyc_get_block_field(self.h, block, pool.encode(), name.encode(), time_level,
                                                       buf.ctypes.data_as(C.c_void_p), buf.nbytes),
                     f"get {pool}.{name}")
@@ -291,7 +292,7 @@ class Dycore:
         nb = self.lib.mpas_dyc_block_field_bytes(self.h, block, pool.encode(), name.encode())
         if nb <= 0:
             raise DycoreError(f"unknown field {pool}.{name}")
-        buf = np.empty(nb // 8, dtype=np.float64)
+        buf = np.empty(nb // 4, dtype=np.int32) if name in F.INT_FIELDS else np.empty(nb // 8, dtype=np.float64)
         self._check(self.lib.mpas_dyc_get_block_field(self.h, block, pool.encode(), name.encode(), time_level,
                                                       buf.ctypes.data_as(C.c_void_p), buf.nbytes),
                     f"get {pool}.{name}")
@@ -437,6 +438,48 @@ class Dycore:
         if flags is None:
             flags = self._diag_flags(w_max, wsp_max, uh_max)
         self._check(self.lib.mpas_dyc_diag_reset(self.h, int(flags)), "diag_reset")
+
+    MICROP_SCHEMES = {None: _lib.MICROP_OFF, "off": _lib.MICROP_OFF, "kessler": _lib.MICROP_KESSLER}
+
+    def field_bytes(self, pool: str, name: str, block: int = 0) -> int:
+        """Bytes of a field's Fortran image (mpas_dyc_field_bytes); 0 for an unknown field and for the
+        device microphysics' fields of a context that never asked for them."""
+        return int(self.lib.mpas_dyc_block_field_bytes(self.h, block, pool.encode(), name.encode()))
+
+    def set_microphysics(self, scheme: str | None = "kessler", index_qc: int = 2, index_qr: int = 3,
+                         bucket_rainnc: float = 0.0):
+        """config_microp_scheme on the device (mpas_dyc_set_microphysics).  ``"kessler"``: every
+        atm_timestep runs driver_microphysics for mp_kessler on time level 2 inside the step (after the
+        negative-scalar clip, before the regional reset and summarize_timestep; captured with the step),
+        so the host neither downloads nor uploads the moist state.  ``index_qc`` / ``index_qr``: the
+        1-based scalar indices of cloud and rain water; ``bucket_rainnc``: config_bucket_rainnc.  It
+        keeps ``diag_physics`` rainnc / rainncv / precipw / i_rainnc, ``diag.surface_pressure`` and
+        ``tend.tend_sfc_pressure`` (zero until updated or set; a restart puts rainnc, i_rainnc and
+        surface_pressure back with set()).  While on, the step runs as with set_physics(tendencies=True)
+        and reads tend.rt_diabatic_tend.  ``None`` / ``"off"``: off again.  Not together with
+        set_physics(microphysics=True).  mpas_dycore.kessler.driver is its host restatement."""
+        if scheme not in self.MICROP_SCHEMES and not isinstance(scheme, int):
+            raise ValueError(f"unknown microphysics scheme {scheme!r} (Thompson and WSM6 stay with the host)")
+        code = scheme if isinstance(scheme, int) and not isinstance(scheme, bool) else self.MICROP_SCHEMES[scheme]
+        self._check(self.lib.mpas_dyc_set_microphysics(self.h, int(code), int(index_qc), int(index_qr),
+                                                       float(bucket_rainnc)), "set_microphysics")
+
+    def microphysics(self, dt: float, time_level: int = 2):
+        """The scheme of set_microphysics once, eagerly and on its own, on ``time_level``
+        (mpas_dyc_microphysics): for tests and hosts that sequence the step themselves.  Asynchronous."""
+        self._check(self.lib.mpas_dyc_microphysics(self.h, float(dt), int(time_level)), "microphysics")
+
+    def microphysics_ms(self, dt: float, time_level: int = 2) -> float:
+        """Milliseconds of one microphysics() call between HIP events (mpas_dyc_get_profile out[7]);
+        synchronous.  The call advances the fields like any other."""
+        self._check(self.lib.mpas_dyc_set_profile(self.h, 1), "set_profile")
+        try:
+            self.microphysics(dt, time_level)
+        finally:
+            self._check(self.lib.mpas_dyc_set_profile(self.h, 0), "set_profile")
+        out = (C.c_double * 8)()
+        self._check(self.lib.mpas_dyc_get_profile(self.h, out, 8), "get_profile")
+        return float(out[7])
 
     def finish_step(self, dt: float):
         """The end of atm_srk3 after the host's microphysics (1672-1794); a no-op unless

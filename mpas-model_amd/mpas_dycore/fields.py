@@ -44,6 +44,12 @@ LOCATION.update(u_amb="edge", theta_amb="cell", rho_amb="cell", scalars_amb="cel
 # the convective running maxima of mpas_dyc_diag_update (diag pool, one value per cell)
 LOCATION.update(w_velocity_max="cell", wind_speed_level1_max="cell", updraft_helicity_max="cell")
 
+# the device microphysics' fields (mpas_dyc_set_microphysics): pool by name, one value per cell
+MICROP_FIELD = {"rainnc": "diag_physics", "rainncv": "diag_physics", "precipw": "diag_physics",
+                "i_rainnc": "diag_physics", "surface_pressure": "diag", "tend_sfc_pressure": "tend"}
+LOCATION.update({n: "cell" for n in MICROP_FIELD})
+INT_FIELDS = {"i_rainnc"}   # int32 on the device, not an index into an element set
+
 VERTICAL_1D = ("fzm", "fzp", "rdzw", "rdzu", "u_init", "v_init")
 SCALARS_0D = ("cf1", "cf2", "cf3")
 

@@ -1,0 +1,414 @@
+"""GPU: the Kessler microphysics on the device (mpas_dyc_set_microphysics / mpas_dyc_microphysics, kessler.hip).
+
+Yardsticks, strongest first:
+* the kernel alone against the compiled reference: the first 64 owned cells are given MPAS-level inputs
+  whose microphysics_from_MPAS is the columns of tests/golden/kessler_columns.npz, and the expected
+  fields are to_mpas / precip_to_mpas (mpas_dycore.kessler, pinned by tests/test_kessler_host.py) of the
+  *fixture's* outputs, i.e. of what the reference's own module_mp_kessler.F computed;
+* the scheme inside the step against the existing host path (MPAS_DYC_PHYSICS_MICROPHYSICS: download, the
+  host restatement, upload, finish_step);
+* structure: graph replay, four blocks against one, off is off, the error paths.
+The device's pow / exp are not the C library's, so parity with the reference is the project's bound
+(rel Linf <= 1e-10; 1e-9 on the mixing ratios, as tests/test_gpu_dropin.py splits them), never bit for
+bit; everything structural is bit for bit.
+"""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import rel_linf
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kessler_columns.npz")
+NS = 3                      # qv, qc, qr
+NFIX = 64                   # the fixture's columns go into the first 64 owned cells
+NSOLVE = 600                # owned cells of the stand-alone runs: cells 600..641 play the halo
+STATE = [("u", "edge"), ("w", "cell"), ("theta_m", "cell"), ("rho_zz", "cell"), ("scalars", "cell")]
+NEW = [("diag_physics", "rainnc"), ("diag_physics", "rainncv"), ("diag_physics", "precipw"),
+       ("diag_physics", "i_rainnc"), ("diag", "surface_pressure"), ("tend", "tend_sfc_pressure")]
+# what one call writes on the owned cells: (pool, name, time level, bound against the reference)
+WRITTEN = [("state", "theta_m", 2, 1e-10), ("state", "scalars", 2, 1e-9), ("diag", "rtheta_p", 1, 1e-10),
+           ("diag", "exner", 1, 1e-10), ("diag", "pressure_p", 1, 1e-10), ("tend", "rt_diabatic_tend", 1, 1e-10),
+           ("diag", "surface_pressure", 1, 1e-10), ("diag_physics", "precipw", 1, 1e-10),
+           ("diag_physics", "rainnc", 1, 1e-10), ("diag_physics", "rainncv", 1, 1e-10),
+           ("tend", "tend_sfc_pressure", 1, 1e-10), ("diag_physics", "i_rainnc", 1, 0.0)]
+STEP_DT = 600.0
+_CASES = {}
+
+
+def _case(K):
+    from mpas_dycore.cases import jw_case
+    if K not in _CASES:
+        _CASES[K] = jw_case(642, K=K, ns=NS, moist=True, cache=False)
+    return _CASES[K]
+
+
+def _img(a):
+    out = np.zeros((a.shape[0] + 1,) + a.shape[1:], dtype=a.dtype)
+    out[:-1] = a
+    return out
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with np.load(GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _mpas_inputs(case, golden, K):
+    """MPAS-level fields of every cell for a stand-alone call: the JW moist state, with the first NFIX
+    cells overwritten so that microphysics_from_MPAS gives the fixture's columns.  zz there is a power of
+    two, so rho = zz rho_zz is the fixture's rho exactly; theta_m -> th is a multiplication undone by a
+    division, within an ulp of the fixture's t."""
+    from mpas_dycore import kessler as ks
+    cols, ref, dt = ks.fixture_columns(golden, K)
+    n = case["nCells"]
+    f = {"zz": np.array(case["zz"], dtype=np.float64), "zgrid": np.array(case["zgrid"], dtype=np.float64),
+         "scalars": np.array(case["scalars"], dtype=np.float64).reshape(n, K, NS)}
+    f["scalars"][:, :, 1:] = 0.0
+    f["rho_zz"] = np.asarray(case["rho"]) / f["zz"]
+    f["theta_m"] = np.asarray(case["theta"]) * (1.0 + ks.R_V / ks.R_D * f["scalars"][:, :, 0])
+    f["rtheta_base"] = np.asarray(case["rho_base"]) / f["zz"] * np.asarray(case["theta_base"])
+    f["exner"] = (f["zz"] * (ks.R_D / ks.P0) * f["rho_zz"] * f["theta_m"]) ** ks.RCV
+    f["exner_base"] = (f["zz"] * (ks.R_D / ks.P0) * f["rtheta_base"]) ** ks.RCV
+    f["pressure_base"] = f["zz"] * ks.R_D * f["exner_base"] * f["rtheta_base"]
+    s = slice(0, NFIX)
+    f["zz"][s] = np.where(np.arange(K)[None, :] % 2 == 0, 1.0, 0.5)
+    f["zgrid"][s] = cols["zgrid"]
+    f["rho_zz"][s] = cols["rho"] / f["zz"][s]
+    f["scalars"][s, :, 0], f["scalars"][s, :, 1], f["scalars"][s, :, 2] = cols["qv"], cols["qc"], cols["qr"]
+    f["theta_m"][s] = cols["t"] * (1.0 + ks.R_V / ks.R_D * np.maximum(0.0, cols["qv"]))
+    f["exner"][s] = cols["pii"]
+    f["rtheta_base"][s] = 0.97 * f["rho_zz"][s] * f["theta_m"][s]
+    f["exner_base"][s] = 0.99 * cols["pii"]
+    f["pressure_base"][s] = 1.0e5 * cols["pii"] ** (ks.CP / ks.R_D)
+    return f, ref, dt
+
+
+def _standalone(case, f, bucket=0.0):
+    """A context of NSOLVE owned cells holding f on time level 2, with a marker in every field the call
+    writes on the cells it must not touch."""
+    from mpas_dycore import Dycore
+    dy = Dycore(case, device=0, moist_end=NS, solve=(NSOLVE, case["nEdges"], case["nVertices"]))
+    dy.set("mesh", "zz", f["zz"])
+    dy.set("mesh", "zgrid", f["zgrid"])
+    dy.set_raw("state", "theta_m", _img(f["theta_m"]), 2)
+    dy.set_raw("state", "rho_zz", _img(f["rho_zz"]), 2)
+    dy.set_raw("state", "scalars", _img(f["scalars"]), 2)
+    for n in ("exner", "rtheta_base", "exner_base", "pressure_base"):
+        dy.set_raw("diag", n, _img(f[n]))
+    dy.set_microphysics("kessler", 2, 3, bucket)
+    return dy
+
+
+def _raw(dy):
+    dy.synchronize()
+    return {(p, n): dy.get_raw(p, n, tl).copy() for p, n, tl, _ in WRITTEN}
+
+
+def _rows(dy, raw, case):
+    """Fortran images -> element-major rows of the owned cells."""
+    K, out = case["nVertLevels"], {}
+    for (p, n), a in raw.items():
+        a = a.reshape(case["nCells"] + 1, -1)
+        out[n] = a.reshape(-1, K, NS) if n == "scalars" else a[:, 0] if a.shape[1] == 1 else a
+    return out
+
+
+KERNEL_KS = (4, 26, 63, 64, 150)
+
+
+@pytest.mark.parametrize("K", KERNEL_KS)
+def test_kernel_against_compiled_reference(golden, K):
+    """One mpas_dyc_microphysics against to_mpas / precip_to_mpas of the compiled reference's outputs on the
+    fixture's 64 columns (every column; nfall 1..34), and against the host restatement on the other
+    owned cells.  K = 4 .. 63: one chunk; 64: two chunks, level 64 alone in the second (lane 63 takes its
+    upstream flux from lane 0 of the next chunk); 150: three chunks in the 192-lane build.
+    Measured rel Linf against the reference on an MI355X, worst over the five K (profiles/kessler_new_tests.log):
+    rt_diabatic_tend 2.7e-14, rtheta_p 9.5e-15, pressure_p 8.3e-15, theta_m 3.4e-16, exner 2.2e-16,
+    surface_pressure 2.7e-16, precipw 1.0e-16, rainnc 2.5e-16 (bound 1e-10); qv 1.2e-16, qc 1.0e-15, qr 3.7e-16
+    (bound 1e-9).  The other owned cells against the restatement: <= 1.0e-14, mixing ratios <= 2.0e-15."""
+    from mpas_dycore import kessler as ks
+    case = _case(K)
+    f, ref, dt = _mpas_inputs(case, golden, K)
+    dy = _standalone(case, f)
+    before = _raw(dy)
+    dy.microphysics(dt, 2)
+    after = _raw(dy)
+    dy.close()
+    got = _rows(dy, after, case)
+    fx = {n: a[:NFIX] for n, a in f.items()}
+    want = ks.driver(fx, dt, scheme_out=ref)
+    rest = {n: a[NFIX:NSOLVE] for n, a in f.items()}
+    want_rest = ks.driver(rest, dt)
+    worst = {}
+    for p, n, tl, tol in WRITTEN:
+        if n in ("i_rainnc", "tend_sfc_pressure", "rainncv"):
+            continue
+        for what, w, sl in (("fixture", want, slice(0, NFIX)), ("rest", want_rest, slice(NFIX, NSOLVE))):
+            names = [(n, Ellipsis)] if n != "scalars" else [("qv", 0), ("qc", 1), ("qr", 2)]
+            for label, idx in names:
+                g = got[n][sl] if idx is Ellipsis else got[n][sl][:, :, idx]
+                e = w[n] if idx is Ellipsis else w[n][:, :, idx]
+                assert np.all(np.isfinite(g)), f"K={K} {what} {label} not finite"
+                err = rel_linf(g, e)
+                worst[(what, label)] = err
+                print(f"K={K} {what} {label}: rel Linf {err:.3e} (bound {tol:g})")
+    for (what, label), err in worst.items():
+        tol = 1e-9 if label in ("qv", "qc", "qr") else 1e-10
+        assert err <= tol, f"K={K} {what} {label}: rel Linf {err:.3e} > {tol:g}"
+    # rainncv is the call's rain, tend_sfc_pressure the change from the old surface_pressure (0)
+    assert np.array_equal(got["rainncv"][:NSOLVE], got["rainnc"][:NSOLVE])
+    assert np.array_equal(got["tend_sfc_pressure"][:NSOLVE], (got["surface_pressure"][:NSOLVE] - 0.0) / dt)
+    assert got["rainnc"][:NFIX].max() > 0.0 and not got["i_rainnc"].any()
+    # the halo cells and the garbage slot hold what they held
+    for (p, n), a in after.items():
+        a, b = a.reshape(case["nCells"] + 1, -1), before[(p, n)].reshape(case["nCells"] + 1, -1)
+        assert np.array_equal(a[NSOLVE:], b[NSOLVE:]), f"{p}.{n}: a halo cell or the garbage slot was written"
+        if n not in ("i_rainnc",):
+            assert not np.array_equal(a[:NSOLVE], b[:NSOLVE]), f"{p}.{n}: nothing written"
+
+
+def test_second_call_accumulates_and_bucket(golden):
+    """rainnc accumulates over calls and rainncv is the call's own; with config_bucket_rainnc the cells
+    whose rainnc passes the bucket move one bucket into i_rainnc (host restatement: kessler.driver)."""
+    from mpas_dycore import kessler as ks
+    K = 26
+    case = _case(K)
+    f, _, dt = _mpas_inputs(case, golden, K)
+    bucket = 0.5 * float(np.median(ks.driver({n: a[:NFIX] for n, a in f.items()}, dt)["rainnc"]))
+    assert bucket > 0.0
+    dy = _standalone(case, f, bucket)
+    dy.microphysics(dt, 2)
+    one = _rows(dy, _raw(dy), case)
+    dy.microphysics(dt, 2)
+    two = _rows(dy, _raw(dy), case)
+    dy.close()
+    h1 = ks.driver({n: a[:NSOLVE] for n, a in f.items()}, dt, bucket_rainnc=bucket)
+    g = {n: a[:NSOLVE] for n, a in f.items()}
+    g.update({n: h1[n] for n in ("theta_m", "scalars", "exner", "rainnc", "i_rainnc", "surface_pressure")})
+    h2 = ks.driver(g, dt, bucket_rainnc=bucket)
+    for got, want, what in ((one, h1, "first"), (two, h2, "second")):
+        assert np.array_equal(got["i_rainnc"][:NSOLVE], want["i_rainnc"]), what
+        for n in ("rainnc", "rainncv", "precipw", "surface_pressure", "tend_sfc_pressure"):
+            err = rel_linf(got[n][:NSOLVE], want[n])
+            print(f"{what} call {n}: rel Linf {err:.3e}")
+            assert err <= 1e-10, f"{what} call {n}: {err:.3e}"
+    assert 0 < one["i_rainnc"][:NFIX].sum() < NFIX and two["i_rainnc"].sum() > one["i_rainnc"].sum()
+    assert not np.array_equal(two["rainncv"], one["rainncv"])
+    assert one["i_rainnc"][NSOLVE:].sum() == 0
+
+
+# ---------------------------------------------------------------------------------------- in the step
+def _seeded(K=26):
+    """Moist JW with cloud and rain seeded in the lower troposphere of every tenth cell."""
+    case = dict(_case(K))
+    n = case["nCells"]
+    sc = np.array(case["scalars"], dtype=np.float64).reshape(n, K, NS)
+    kk = np.arange(K)[None, :]
+    patch = (np.arange(n) % 10 == 0)[:, None]
+    sc[:, :, 1] = np.where(patch & (kk >= 2) & (kk < 10), 1.0e-3, 0.0)
+    sc[:, :, 2] = np.where(patch & (kk >= 1) & (kk < 8), 2.0e-3 * (1.0 + np.sin(np.arange(n)))[:, None], 0.0)
+    case["scalars"] = sc.reshape(np.asarray(case["scalars"]).shape)
+    return case
+
+
+def _state(dy, block=None):
+    dy.synchronize()
+    return {n: dy.get("state", n, 1) for n, _ in STATE}
+
+
+def _new_fields(dy, block=0):
+    return {n: dy.get(p, n, 1, block=block).astype(np.float64) for p, n in NEW}
+
+
+def _run_device(case, nsteps, graph=False, toggle=False, on=True):
+    from mpas_dycore import Dycore
+    dy = Dycore(case, device=0, moist_end=NS)
+    dy.init_diagnostics(STEP_DT)
+    dy.use_graph(graph)
+    if on:
+        dy.set_microphysics("kessler", 2, 3)
+    if toggle:
+        dy.set_microphysics("kessler", 2, 3)
+        dy.set_microphysics(None)
+    out, caps = [], []
+    for it in range(1, nsteps + 1):
+        dy.atm_timestep(STEP_DT, it)
+        assert dy.graph_active() == bool(graph)
+        caps.append(dy.graph_captures())
+        dy.shift_time_levels()
+        out.append(_state(dy))
+    new = _new_fields(dy) if on else None
+    dy.close()
+    return out, new, caps
+
+
+_RUNS = {}
+
+
+def _device_run(nsteps=3):
+    if "device" not in _RUNS:
+        _RUNS["device"] = _run_device(_seeded(), nsteps)
+    return _RUNS["device"]
+
+
+def test_in_the_step_against_host_microphysics():
+    """Three steps with the device scheme on against the same run on the host path
+    (set_physics(tendencies, microphysics): after each step download, kessler.driver, upload, finish_step).
+    Bounds: 1e-10 on u, theta_m, rho_zz, 1e-9 on w and scalars; the run with the scheme off differs by
+    more than 1e-8 in theta_m, so the comparison cannot pass on trivia.
+    Measured on an MI355X (worst of the three steps): u 1.6e-14, w 1.8e-14, theta_m 7.6e-15, rho_zz 5.5e-16,
+    scalars 3.6e-14; rainnc, precipw, surface_pressure after the third step <= 5.3e-16."""
+    from mpas_dycore import Dycore, kessler as ks
+    case = _seeded()
+    K, n = case["nVertLevels"], case["nCells"]
+    dev, new, _ = _device_run()
+    dy = Dycore(case, device=0, moist_end=NS)
+    dy.init_diagnostics(STEP_DT)
+    dy.set_physics(tendencies=True, microphysics=True)
+    static = {"zz": np.asarray(case["zz"]), "zgrid": np.asarray(case["zgrid"]),
+              "rtheta_base": dy.get("diag", "rtheta_base"), "exner_base": dy.get("diag", "exner_base"),
+              "pressure_base": dy.get("diag", "pressure_base")}
+    acc = {"rainnc": np.zeros(n), "i_rainnc": np.zeros(n, dtype=np.int32), "surface_pressure": np.zeros(n)}
+    resplit = nfall_max = 0
+    for it in range(1, 4):
+        dy.atm_timestep(STEP_DT, it)
+        dy.synchronize()
+        f = dict(static, **acc, theta_m=dy.get("state", "theta_m", 2), rho_zz=dy.get("state", "rho_zz", 2),
+                 scalars=dy.get("state", "scalars", 2), exner=dy.get("diag", "exner"))
+        o = ks.driver(f, STEP_DT)
+        resplit += int(o["info"]["resplit"].sum())
+        nfall_max = max(nfall_max, int(o["info"]["nfall0"].max()))
+        acc = {k: o[k] for k in acc}
+        dy.set_raw("state", "theta_m", _img(o["theta_m"]), 2)
+        dy.set_raw("state", "scalars", _img(o["scalars"]), 2)
+        for p, nm in (("diag", "rtheta_p"), ("diag", "exner"), ("diag", "pressure_p"), ("tend", "rt_diabatic_tend")):
+            dy.set_raw(p, nm, _img(o[nm]))
+        dy.finish_step(STEP_DT)
+        dy.shift_time_levels()
+        host = _state(dy)
+        for nm, _ in STATE:
+            tol = 1e-9 if nm in ("w", "scalars") else 1e-10
+            err = rel_linf(dev[it - 1][nm], host[nm])
+            print(f"step {it} {nm}: rel Linf {err:.3e} (bound {tol:g})")
+            assert err <= tol, f"step {it} {nm}: rel Linf {err:.3e} > {tol:g}"
+    dy.close()
+    assert resplit > 0 and nfall_max > 8                      # the data-dependent loop was exercised
+    for nm in ("rainnc", "precipw", "surface_pressure"):
+        err = rel_linf(new[nm][:, 0], o[nm])
+        print(f"after 3 steps {nm}: rel Linf {err:.3e}")
+        assert err <= 1e-10, f"{nm}: {err:.3e}"
+    assert new["rainnc"].max() > 0.0
+    off, _, _ = _run_device(case, 3, on=False)
+    assert rel_linf(off[-1]["theta_m"], dev[-1]["theta_m"]) > 1e-8
+
+
+def test_graph_replay_equals_eager():
+    """The scheme is captured with the step (its split loop is inside the kernel): replayed steps are the
+    eager steps bit for bit, and mpas_dyc_get_profile out[5] stops growing after one capture per
+    time-level parity."""
+    eager, new_e, caps_e = _device_run()
+    graph, new_g, caps = _run_device(_seeded(), 5, graph=True)
+    assert caps_e == [0, 0, 0] and caps == [1, 2, 2, 2, 2], caps
+    for it in range(3):
+        for n, _ in STATE:
+            assert np.array_equal(eager[it][n], graph[it][n]), f"step {it + 1} {n}"
+
+
+def test_four_blocks_equal_one_block():
+    """Bit for bit after three steps on the prognostics and the new fields: the kernel writes owned
+    cells only, and the start-of-step exchange (theta_m, scalars, pressure_p, rtheta_p, exner) covers
+    everything the scheme changes that a neighbour reads."""
+    from mpas_dycore import Dycore, decomp
+    case = _seeded()
+    one, new_one, _ = _device_run()
+    blocks = decomp.decompose(case, decomp.partition_sfc(case["nCells"], 4))
+    dy = Dycore.from_blocks(blocks, device=0, moist_end=NS)
+    dy.init_diagnostics(STEP_DT)
+    dy.set_microphysics("kessler", 2, 3)
+    n_glob = {"cell": case["nCells"], "edge": case["nEdges"]}
+    for it in range(1, 4):
+        dy.atm_timestep(STEP_DT, it)
+        dy.shift_time_levels()
+        dy.synchronize()
+        for n, loc in STATE:
+            got = decomp.gather_owned(blocks, [dy.get("state", n, 1, block=i) for i in range(4)], loc, n_glob[loc])
+            assert np.array_equal(got, one[it - 1][n]), f"step {it} {n}"
+    for p, n in NEW:
+        got = decomp.gather_owned(blocks, [dy.get(p, n, 1, block=i).astype(np.float64) for i in range(4)], "cell",
+                                  n_glob["cell"])
+        assert np.array_equal(got, new_one[n]), n
+    dy.close()
+
+
+def test_off_is_off():
+    """Without the switch the context holds none of the new fields, and a context that set the switch
+    on and off again steps bit for bit like one that never did."""
+    from mpas_dycore import Dycore
+    case = _seeded()
+    dy = Dycore(case, device=0, moist_end=NS)
+    for p, n in NEW:
+        assert dy.field_bytes(p, n) == 0, (p, n)
+        assert not dy.lib.mpas_dyc_field_device_ptr(dy.h, p.encode(), n.encode(), 1)
+    dy.set_microphysics("kessler", 2, 3)
+    assert dy.field_bytes("diag_physics", "rainnc") == 8 * (case["nCells"] + 1)
+    assert dy.field_bytes("diag_physics", "i_rainnc") == 4 * (case["nCells"] + 1)
+    assert dy.lib.mpas_dyc_field_device_ptr(dy.h, b"diag_physics", b"rainnc", 1)
+    assert not dy.get("diag_physics", "rainnc").any()
+    dy.close()
+    # a restart's set_field allocates them too
+    dy = Dycore(case, device=0, moist_end=NS)
+    r = np.linspace(0.0, 5.0, case["nCells"])
+    dy.set("diag_physics", "rainnc", r)
+    assert np.array_equal(dy.get("diag_physics", "rainnc")[:, 0], r)
+    assert not dy.get("diag_physics", "i_rainnc").any() and not dy.get("diag", "surface_pressure").any()
+    dy.close()
+    plain, _, _ = _run_device(case, 3, on=False)
+    toggled, _, _ = _run_device(case, 3, on=False, toggle=True)
+    for it in range(3):
+        for n, _ in STATE:
+            assert np.array_equal(plain[it][n], toggled[it][n]), f"step {it + 1} {n}"
+
+
+def test_error_paths():
+    from mpas_dycore import Dycore, DycoreError, _lib
+    case = _case(26)
+    dy = Dycore(case, device=0, moist_end=NS)
+    lib, h = dy.lib, dy.h
+    EINVAL, ESTATE = -1, -3
+    assert lib.mpas_dyc_set_microphysics(h, 2, 2, 3, 0.0) == EINVAL           # unknown scheme
+    assert lib.mpas_dyc_set_microphysics(h, -1, 2, 3, 0.0) == EINVAL
+    for qc, qr in ((0, 3), (2, 4), (4, 2), (2, 0), (2, 2), (1, 3), (2, 1)):   # range, equal, index_qv = 1
+        assert lib.mpas_dyc_set_microphysics(h, _lib.MICROP_KESSLER, qc, qr, 0.0) == EINVAL, (qc, qr)
+    assert lib.mpas_dyc_microphysics(h, 600.0, 2) == ESTATE                   # no scheme set
+    assert dy.field_bytes("diag_physics", "rainnc") == 0                      # the failures allocated nothing
+    # both owners of the microphysics, in either order
+    dy.set_microphysics("kessler", 2, 3)
+    assert lib.mpas_dyc_set_physics(h, Dycore.PHYSICS_TENDENCIES | Dycore.PHYSICS_MICROPHYSICS) != 0
+    dy.set_physics(tendencies=True)
+    assert lib.mpas_dyc_microphysics(h, 0.0, 2) == EINVAL and lib.mpas_dyc_microphysics(h, 600.0, 3) == EINVAL
+    dy.set_microphysics(None)
+    dy.set_physics(tendencies=True, microphysics=True)
+    assert lib.mpas_dyc_set_microphysics(h, _lib.MICROP_KESSLER, 2, 3, 0.0) != 0
+    with pytest.raises(DycoreError):
+        dy.set_microphysics("kessler", 2, 3)
+    with pytest.raises(ValueError):
+        dy.set_microphysics("thompson")
+    dy.close()
+    # a host-only context keeps the switch, allocates nothing, and cannot run the scheme
+    import ctypes as C
+    from mpas_dycore.dycore import _make_dims
+    dims = _make_dims([case], [None], NS)
+    cfg = _lib.make_config(case["config"])
+    hh = C.c_void_p()
+    assert lib.mpas_dyc_create_blocks(1, dims, C.byref(cfg), _lib.HOST_ONLY, C.byref(hh)) == 0
+    try:
+        assert lib.mpas_dyc_set_microphysics(hh, _lib.MICROP_KESSLER, 2, 3, 0.0) == 0
+        assert lib.mpas_dyc_field_bytes(hh, b"diag_physics", b"rainnc") == 0
+        assert lib.mpas_dyc_microphysics(hh, 600.0, 2) == ESTATE
+        assert lib.mpas_dyc_set_microphysics(hh, 7, 2, 3, 0.0) == EINVAL
+    finally:
+        lib.mpas_dyc_destroy(hh)
