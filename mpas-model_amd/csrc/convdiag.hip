@@ -12,7 +12,7 @@
 //  * zeta(k,i).  The reference scatters kiteAreasOnVertex(j,v) * vorticity(k,v) into cellsOnVertex(j,v)
 //    for v = 1..nVertices, j = 1..3, from 0.0.  A cell's terms therefore arrive in ascending block-local
 //    vertex index (then j), not in verticesOnCell order.  The host builds that list per owned cell
-//    from cellsOnVertex (ConvDiag::cv_start / cv_kite, dycore.hip convdiag_table); an entry is the
+//    from cellsOnVertex (ConvDiag::cv_start / cv_kite, physics_host.hip convdiag_table); an entry is the
 //    index 3 v + j into kiteAreasOnVertex, v = entry / 3.  Entries of the garbage cell are dropped.
 //  * uph(i) = sum over k = 1..K of uh(k,i) * max(0, min(z_agl(k+1), 5000) - max(z_agl(k), 2000)),
 //    z_agl(k) = zgrid(k,i) - zgrid(1,i), added in ascending k from 0.0.  Each lane forms the term of
@@ -39,6 +39,21 @@ constexpr int CONVDIAG_THREADS = 256;
 constexpr int CONVDIAG_WAVES = CONVDIAG_THREADS / 64;
 // = MPAS_DYC_DIAG_* of include/mpas_dycore.h
 constexpr int CONVDIAG_W = 1, CONVDIAG_WSP = 2, CONVDIAG_UH = 4;
+// the diag fields of mpas_dyc_diag_update, in the bit order of the flags
+constexpr const char* CONVDIAG_FIELDS[3] = {"w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max"};
+
+// The hook's host state (mpas_dyc_ctx::convdiag): the MPAS_DYC_DIAG_* mask mpas_dyc_diag_update applies,
+// and the last mpas_dyc_diag_update under mpas_dyc_set_profile (mpas_dyc_get_profile out[6])
+struct ConvDiagState {
+  int flags = 0;
+  double ms = 0.0;
+};
+// A block's table (Block::cv; physics_host.hip convdiag_table), on the device: per owned cell its
+// (vertex, j) pairs in ascending vertex index, as 3 v + j
+struct ConvDiagTable {
+  int *start = nullptr, *kite = nullptr;
+  bool ready = false;
+};
 
 struct ConvDiag {
   int nCellsSolve, K, flags;

@@ -41,6 +41,22 @@ namespace {
 
 enum Loc { L_CELL, L_EDGE, L_VERTEX, L_NONE };
 enum Target { T_NONE, T_CELL, T_EDGE, T_VERTEX, T_SMALL };  // int index semantics
+// When a field's buffers are allocated.  G_ALWAYS: with the context.  G_ON_SET: at its own first
+// set_field, by that field alone -- the inputs only the model-init precompute and the reconstruction
+// coefficients read (mpas_dyc_model_init, mpas_dyc_init_reconstruct).  The others belong to a step hook
+// (physics_host.hip) and are allocated together, zeroed, by alloc_group: when the hook is switched on,
+// or at the first set_field of one of them.
+enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP };
+// all_blocks: a first set_field completes the group on every block (false: on that block only).
+// hidden: mpas_dyc_block_field_bytes reports 0 until the field is allocated -- the fields are held
+// only by a context that asked for them.
+constexpr struct { bool all_blocks, hidden; } GROUPS[] = {
+    {false, false}, {false, false},  // G_ALWAYS, G_ON_SET: neither applies
+    {false, false},  // G_IAU_INCR: the tend_iau pool, the analysis increments
+    {false, false},  // G_IAU_SUMS: scratch.iau_*, the library's own; mpas_dyc_set_iau(on) allocates them
+    {true, false},   // G_CONVDIAG: the convective running maxima
+    {true, true},    // G_MICROP: the device microphysics' own fields
+};
 
 struct Field {
   std::string pool, name;
@@ -61,9 +77,7 @@ struct Field {
   int me = 0;
   void* packed = nullptr;
   int64_t packed_inner = 0;
-  // allocated at its first set_field: the inputs only the model-init precompute reads (deriv_two, zb,
-  // zb3, meshDensity, areaCell, areaTriangle -- mpas_dyc_model_init)
-  bool lazy = false;
+  Group group = G_ALWAYS;  // given where build_registry adds the field
 };
 
 // One entry of a block's multihalo exchange list (mpas_multihalo_exchange_list:
@@ -91,12 +105,9 @@ struct Block {
   std::vector<int32_t> h_coe, h_eoc, h_noc;  // host copies (0-based) for the halo-boundary flags
   std::vector<int32_t> h_voe, h_eov;         // verticesOnEdge / edgesOnVertex (0-based): fused u unpack
   std::vector<int32_t> h_noe;                // nEdgesOnEdge (pack_mesh)
-  // cellsOnVertex (0-based), and the table the convective running maxima derive from it
-  // (convdiag_table): per owned cell its (vertex, j) pairs in ascending vertex index, as 3 v + j
+  // cellsOnVertex (0-based), and the table the convective running maxima derive from it (convdiag_table)
   std::vector<int32_t> h_cov;
-  int* cv_start = nullptr;
-  int* cv_kite = nullptr;
-  bool cv_ready = false;
+  ConvDiagTable cv;
   // maxEdges / maxEdges2 as the host declared them (the mesh file's dimensions; Fortran images and
   // h_eoc use these strides).  d.maxEdges / d.maxEdges2 are the strides the kernels index with:
   // max(nEdgesOnCell) and the edgesOnEdge slots the kernels need after pack_mesh
@@ -269,29 +280,11 @@ struct mpas_dyc_ctx {
   // default is config_print_global_minmax_vel = true, Registry.xml:339)
   int summary_flags = MPAS_DYC_PRINT_GLOBAL_MINMAX_VEL;
   int summary_tl = 0;                   // time level the records describe (0: none yet)
-  // incremental analysis update (mpas_dyc_set_iau; iau.hip): config_IAU_option / _window_length_s, and
-  // atm_iau_coef of the step being enqueued (> 1e-12: the step applies the forcing).  iau_stale: the
-  // library's own tendencies (scratch.iau_*, tend.scalars_tend of a host that supplies none) hold a
-  // forced step's sums and are zeroed before the next unforced one reads them
-  int iau_on = 0;
-  double iau_window = 0.0, iau_wgt = 0.0;
-  bool iau_stale = false;
+  // the step hooks (physics_host.hip), each with its state struct next to its kernels
+  IauState iau;                         // incremental analysis update (mpas_dyc_set_iau; iau.hip)
+  ConvDiagState convdiag;               // the convective running maxima (mpas_dyc_set_diag_update; convdiag.hip)
+  MicropState microp;                   // the device microphysics (mpas_dyc_set_microphysics; kessler.hip)
   int64_t graph_captures = 0;           // steps captured so far (mpas_dyc_get_profile out[5])
-  // the convective running maxima (mpas_dyc_set_diag_update; convdiag.hip): the MPAS_DYC_DIAG_* mask
-  // mpas_dyc_diag_update applies, and whether diag.w_velocity_max / wind_speed_level1_max /
-  // updraft_helicity_max are allocated (at the first non-zero mask or set_field of one of them)
-  int diag_flags = 0;
-  bool diag_alloc = false;
-  double diag_ms = 0.0;                 // the last mpas_dyc_diag_update under mpas_dyc_set_profile (out[6])
-  // the device microphysics (mpas_dyc_set_microphysics; kessler.hip): the MPAS_DYC_MICROP_* scheme of
-  // the step, the 0-based scalar indices of cloud and rain water, config_bucket_rainnc, and whether
-  // diag_physics.rainnc / rainncv / precipw / i_rainnc, diag.surface_pressure and
-  // tend.tend_sfc_pressure are allocated (when the switch first goes on, or at a set_field of one of them)
-  int microp = 0;
-  int mp_iqc = -1, mp_iqr = -1;
-  double mp_bucket = 0.0;
-  bool mp_alloc = false;
-  double microp_ms = 0.0;               // the last mpas_dyc_microphysics under mpas_dyc_set_profile (out[7])
   bool tail_pending = false;            // MPAS_DYC_PHYSICS_MICROPHYSICS: a step ran, mpas_dyc_finish_step not yet
   // exchange profile (mpas_dyc_set_profile): eager steps with HIP events around the exposed part of
   // every exchange (a blocking exchange whole; a split-phase one from the compute stream reaching
@@ -351,8 +344,9 @@ bool is_host_0d(const Field& f) {
   return f.pool == "mesh" && (f.name == "cf1" || f.name == "cf2" || f.name == "cf3");
 }
 
-void add(Block& c, const char* pool, const char* name, Loc loc, int64_t inner, int ntl = 1, bool is_int = false,
-         Target t = T_NONE) {
+// returns the new field: `add(...).group = G_...` for one that is not allocated with the context
+Field& add(Block& c, const char* pool, const char* name, Loc loc, int64_t inner, int ntl = 1, bool is_int = false,
+           Target t = T_NONE) {
   Field f;
   f.pool = pool;
   f.name = name;
@@ -363,19 +357,7 @@ void add(Block& c, const char* pool, const char* name, Loc loc, int64_t inner, i
   f.ntl = ntl;
   c.by_name[f.pool + "." + f.name] = (int)c.fields.size();
   c.fields.push_back(f);
-}
-// the fields of mpas_dyc_diag_update, in the bit order of MPAS_DYC_DIAG_*
-const char* const CONVDIAG_FIELDS[3] = {"w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max"};
-bool is_convdiag(const Field& f) {
-  if (f.pool != "diag") return false;
-  for (const char* n : CONVDIAG_FIELDS)
-    if (f.name == n) return true;
-  return false;
-}
-// the fields only the device microphysics touches (mpas_dyc_set_microphysics)
-bool is_microp(const Field& f) {
-  if (f.pool == "diag_physics") return true;
-  return (f.pool == "diag" && f.name == "surface_pressure") || (f.pool == "tend" && f.name == "tend_sfc_pressure");
+  return c.fields.back();
 }
 // The Registry.xml var_structs the dycore touches (same list the oracle harness builds).
 void build_registry(Block& c) {
@@ -508,54 +490,44 @@ void build_registry(Block& c) {
     c.fields[b].rot = a;
   }
   // inputs of the model-init precompute (mpas_dyc_model_init), allocated when set
-  add(c, "mesh", "deriv_two", L_EDGE, 30);
-  add(c, "mesh", "zb", L_EDGE, 2 * (int64_t)(K + 1));
-  add(c, "mesh", "zb3", L_EDGE, 2 * (int64_t)(K + 1));
-  add(c, "mesh", "meshDensity", L_CELL, 1);
-  add(c, "mesh", "areaCell", L_CELL, 1);
-  add(c, "mesh", "areaTriangle", L_VERTEX, 1);
+  add(c, "mesh", "deriv_two", L_EDGE, 30).group = G_ON_SET;
+  add(c, "mesh", "zb", L_EDGE, 2 * (int64_t)(K + 1)).group = G_ON_SET;
+  add(c, "mesh", "zb3", L_EDGE, 2 * (int64_t)(K + 1)).group = G_ON_SET;
+  add(c, "mesh", "meshDensity", L_CELL, 1).group = G_ON_SET;
+  add(c, "mesh", "areaCell", L_CELL, 1).group = G_ON_SET;
+  add(c, "mesh", "areaTriangle", L_VERTEX, 1).group = G_ON_SET;
   // optional: the C library's values of the two transcendental functions of the precompute, which the
   // caller computes as the compiled reference does (meshDensity**0.25 per cell and per edge midpoint,
   // the damping layer's sin per cell and level); unset, the device uses correctly rounded ones
-  add(c, "mesh", "meshDensity_root4", L_CELL, 1);
-  add(c, "mesh", "meshDensityEdge_root4", L_EDGE, 1);
-  add(c, "mesh", "dss_sin", L_CELL, K);
+  add(c, "mesh", "meshDensity_root4", L_CELL, 1).group = G_ON_SET;
+  add(c, "mesh", "meshDensityEdge_root4", L_EDGE, 1).group = G_ON_SET;
+  add(c, "mesh", "dss_sin", L_CELL, K).group = G_ON_SET;
   // inputs of the reconstruction coefficients (mpas_dyc_init_reconstruct), allocated when set
-  for (const char* n : {"xCell", "yCell", "zCell"}) add(c, "mesh", n, L_CELL, 1);
-  for (const char* n : {"xEdge", "yEdge", "zEdge"}) add(c, "mesh", n, L_EDGE, 1);
-  for (const char* n : {"deriv_two", "zb", "zb3", "meshDensity", "areaCell", "areaTriangle", "xCell", "yCell", "zCell",
-                        "xEdge", "yEdge", "zEdge", "meshDensity_root4", "meshDensityEdge_root4", "dss_sin"})
-    c.fields[c.by_name[std::string("mesh.") + n]].lazy = true;
+  for (const char* n : {"xCell", "yCell", "zCell"}) add(c, "mesh", n, L_CELL, 1).group = G_ON_SET;
+  for (const char* n : {"xEdge", "yEdge", "zEdge"}) add(c, "mesh", n, L_EDGE, 1).group = G_ON_SET;
   // the tend_iau pool (Registry.xml:3101-3132): the analysis increments of the incremental analysis
   // update, and the step's physics + IAU tendencies (iau.hip); allocated, zeroed, at the first
-  // set_field of the pool or at mpas_dyc_set_iau(on)
-  add(c, "tend_iau", "u", L_EDGE, K);
-  add(c, "tend_iau", "theta", L_CELL, K);
-  add(c, "tend_iau", "rho", L_CELL, K);
-  add(c, "tend_iau", "scalars", L_CELL, (int64_t)ns * K);
+  // set_field of the pool (the increments of that block) or at mpas_dyc_set_iau(on)
+  add(c, "tend_iau", "u", L_EDGE, K).group = G_IAU_INCR;
+  add(c, "tend_iau", "theta", L_CELL, K).group = G_IAU_INCR;
+  add(c, "tend_iau", "rho", L_CELL, K).group = G_IAU_INCR;
+  add(c, "tend_iau", "scalars", L_CELL, (int64_t)ns * K).group = G_IAU_INCR;
   c.fields.back().nsub = ns;
-  add(c, "scratch", "iau_ru", L_EDGE, K);
-  add(c, "scratch", "iau_rtheta", L_CELL, K);
-  add(c, "scratch", "iau_rho", L_CELL, K);
-  for (const char* n : {"tend_iau.u", "tend_iau.theta", "tend_iau.rho", "tend_iau.scalars", "scratch.iau_ru",
-                        "scratch.iau_rtheta", "scratch.iau_rho"})
-    c.fields[c.by_name[n]].lazy = true;
+  add(c, "scratch", "iau_ru", L_EDGE, K).group = G_IAU_SUMS;
+  add(c, "scratch", "iau_rtheta", L_CELL, K).group = G_IAU_SUMS;
+  add(c, "scratch", "iau_rho", L_CELL, K).group = G_IAU_SUMS;
   // the running maxima of convective_diagnostics_update (Registry.xml diag: (nCells + 1) each):
   // allocated, zeroed, at the first set_field of one of them or at mpas_dyc_set_diag_update with a
-  // non-zero mask (convdiag_alloc)
-  for (const char* n : CONVDIAG_FIELDS) {
-    add(c, "diag", n, L_CELL, 1);
-    c.fields.back().lazy = true;
-  }
+  // non-zero mask
+  for (const char* n : {CONVDIAG_FIELDS[0], CONVDIAG_FIELDS[1], CONVDIAG_FIELDS[2]})
+    add(c, "diag", n, L_CELL, 1).group = G_CONVDIAG;
   // the device microphysics' own fields (Registry.xml diag_physics / diag / tend: (nCells + 1) each):
   // allocated, zeroed, at the first set_field of one of them or when mpas_dyc_set_microphysics turns
-  // a scheme on (microp_alloc)
-  for (const char* n : {"rainnc", "rainncv", "precipw"}) add(c, "diag_physics", n, L_CELL, 1);
-  add(c, "diag_physics", "i_rainnc", L_CELL, 1, 1, true);
-  add(c, "diag", "surface_pressure", L_CELL, 1);
-  add(c, "tend", "tend_sfc_pressure", L_CELL, 1);
-  for (auto& f : c.fields)
-    if (is_microp(f)) f.lazy = true;
+  // a scheme on
+  for (const char* n : {"rainnc", "rainncv", "precipw"}) add(c, "diag_physics", n, L_CELL, 1).group = G_MICROP;
+  add(c, "diag_physics", "i_rainnc", L_CELL, 1, 1, true).group = G_MICROP;
+  add(c, "diag", "surface_pressure", L_CELL, 1).group = G_MICROP;
+  add(c, "tend", "tend_sfc_pressure", L_CELL, 1).group = G_MICROP;
   // the maxEdges- and maxEdges2-strided mesh arrays (pack_mesh)
   for (const char* n : {"edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "coeffs_reconstruct",
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
@@ -589,14 +561,14 @@ T* P(mpas_dyc_ctx* c, Block& b, const char* pool, const char* name, int tl = 1) 
 // DO_PHYSICS coupling of the step: the host's flag, or implied by the incremental analysis update
 // or by the device microphysics
 bool physics_tendencies(const mpas_dyc_ctx* c) {
-  return (c->physics & MPAS_DYC_PHYSICS_TENDENCIES) || c->iau_on || c->microp;
+  return (c->physics & MPAS_DYC_PHYSICS_TENDENCIES) || c->iau.on || c->microp.scheme;
 }
 // the step being enqueued applies the IAU forcing (mpas_atm_iau.F:118)
-bool iau_active(const mpas_dyc_ctx* c) { return c->iau_on && c->iau_wgt > 1.0e-12; }
+bool iau_active(const mpas_dyc_ctx* c) { return c->iau.on && c->iau.wgt > 1.0e-12; }
 // Ptrs::tend_*_physics are the library's sums (scratch.iau_*): in a forced step, and in every step of
 // a host that supplies no physics tendencies (then they hold the zeros it would have supplied)
 bool iau_sums(const mpas_dyc_ctx* c) {
-  return c->iau_on && (iau_active(c) || !(c->physics & MPAS_DYC_PHYSICS_TENDENCIES));
+  return c->iau.on && (iau_active(c) || !(c->physics & MPAS_DYC_PHYSICS_TENDENCIES));
 }
 
 Ptrs make_ptrs(mpas_dyc_ctx* c, Block& b) {
@@ -719,17 +691,6 @@ inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + WAVES_PER_BLOCK - 
   } while (0)
 
 // captured steps bake pointers, list lengths and flags in: drop them when any of those changes
-void drop_graphs(mpas_dyc_ctx* ctx);
-// the tend_iau pool of a block, zeroed (sums: and the step's physics + IAU arrays, scratch.iau_*)
-int iau_alloc(mpas_dyc_ctx* ctx, Block& b, bool sums) {
-  for (auto& f : b.fields) {
-    if (f.buf[0] || !(f.pool == "tend_iau" || (sums && f.pool == "scratch" && f.name.compare(0, 4, "iau_") == 0))) continue;
-    const int64_t nb = field_bytes(b, f) + 256;
-    HIPCHK(hipMalloc(&f.buf[0], nb));
-    HIPCHK(hipMemset(f.buf[0], 0, nb));
-  }
-  return MPAS_DYC_OK;
-}
 void drop_graphs(mpas_dyc_ctx* ctx) {
   for (auto& kv : ctx->graphs)
     if (kv.second) (void)hipGraphExecDestroy(kv.second);
@@ -737,104 +698,54 @@ void drop_graphs(mpas_dyc_ctx* ctx) {
   ctx->graph_dt.clear();
 }
 
-// The running maxima's derived table of one block: for each owned cell the (vertex, j) pairs with
-// cellsOnVertex(j, vertex) = cell, in ascending vertex index and then j -- the order in which the
-// reference's scatter over the vertices (convective_diagnostics.F:169-174) adds a cell's terms --
-// stored as 3 vertex + j.  Pairs of halo cells and of the garbage cell are dropped.  Rebuilt like
-// the other derived tables: setting cellsOnVertex clears cv_ready (and bnd_ready).
-int convdiag_table(mpas_dyc_ctx* ctx, Block& b) {
-  const Dims& d = b.d;
-  if ((int64_t)b.h_cov.size() < 3LL * d.nVertices) {
-    ctx->err = "mesh.cellsOnVertex not set";
-    return MPAS_DYC_ESTATE;
-  }
-  if (3LL * ((int64_t)d.nVertices + 1) > INT32_MAX) {
-    ctx->err = "too many vertices for the convective diagnostics' table";
-    return MPAS_DYC_EINVAL;
-  }
-  std::vector<int32_t> start((size_t)d.nCellsSolve + 1, 0);
-  for (int64_t i = 0; i < 3LL * d.nVertices; ++i)
-    if (b.h_cov[i] < d.nCellsSolve) ++start[b.h_cov[i] + 1];
-  for (int c = 0; c < d.nCellsSolve; ++c) start[c + 1] += start[c];
-  std::vector<int32_t> fill(start.begin(), start.end() - 1), kite((size_t)std::max(1, start[d.nCellsSolve]));
-  for (int64_t i = 0; i < 3LL * d.nVertices; ++i)  // ascending (vertex, j)
-    if (b.h_cov[i] < d.nCellsSolve) kite[fill[b.h_cov[i]]++] = (int32_t)i;
-  HIPCHK(hipStreamSynchronize(ctx->stream));  // a running update still reads the old table
-  if (b.cv_start) (void)hipFree(b.cv_start);
-  if (b.cv_kite) (void)hipFree(b.cv_kite);
-  b.cv_start = b.cv_kite = nullptr;
-  HIPCHK(hipMalloc(&b.cv_start, start.size() * 4));
-  HIPCHK(hipMalloc(&b.cv_kite, kite.size() * 4));
-  HIPCHK(hipMemcpy(b.cv_start, start.data(), start.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b.cv_kite, kite.data(), kite.size() * 4, hipMemcpyHostToDevice));
-  b.cv_ready = true;
-  return MPAS_DYC_OK;
+// entry points that move fields or enqueue work on them: a host-only context (the planner's) has none
+int require_device(mpas_dyc_ctx* ctx) {
+  if (!ctx->host_only) return MPAS_DYC_OK;
+  ctx->err = "host-only context holds no fields";
+  return MPAS_DYC_ESTATE;
 }
 
-// diag.w_velocity_max / wind_speed_level1_max / updraft_helicity_max of every block, zeroed
-int convdiag_alloc(mpas_dyc_ctx* ctx) {
-  for (auto& b : ctx->blk)
-    for (auto& f : b.fields) {
-      if (f.buf[0] || !is_convdiag(f)) continue;
-      const int64_t nb = field_bytes(b, f) + 256;
-      HIPCHK(hipMalloc(&f.buf[0], nb));
-      HIPCHK(hipMemsetAsync(f.buf[0], 0, nb, ctx->stream));  // ordered before the stream's updates and resets
-    }
-  HIPCHK(hipStreamSynchronize(ctx->stream));  // and before a set_field / get_field of the caller
-  ctx->diag_alloc = true;
+// A field's first buffer with its 256 B of slack (mpas_dyc_create_blocks), zeroed on the compute stream
+int alloc_field(mpas_dyc_ctx* ctx, Block& b, Field& f, bool zero) {
+  const int64_t nb = field_bytes(b, f) + 256;
+  HIPCHK(hipMalloc(&f.buf[0], nb));
+  if (zero) HIPCHK(hipMemsetAsync(f.buf[0], 0, nb, ctx->stream));  // ordered before the stream's own work on it
   return MPAS_DYC_OK;
 }
-
-// the device microphysics' fields of every block, zeroed
-int microp_alloc(mpas_dyc_ctx* ctx) {
-  for (auto& b : ctx->blk)
-    for (auto& f : b.fields) {
-      if (f.buf[0] || !is_microp(f)) continue;
-      const int64_t nb = field_bytes(b, f) + 256;
-      HIPCHK(hipMalloc(&f.buf[0], nb));
-      HIPCHK(hipMemsetAsync(f.buf[0], 0, nb, ctx->stream));
-    }
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->mp_alloc = true;
-  return MPAS_DYC_OK;
-}
-
-// driver_microphysics for mp_kessler on time level tl of every block: one launch per block
-int kessler_enqueue(mpas_dyc_ctx* ctx, double dt, int tl) {
-  if (ctx->planning) return MPAS_DYC_OK;
+// Every field of a group that has no buffer yet, on every block or on `only`, zeroed.  A call that
+// fails half-way leaves the rest unallocated (group_ready stays false), and the next one completes it.
+int alloc_group(mpas_dyc_ctx* ctx, Group g, Block* only = nullptr) {
   for (auto& b : ctx->blk) {
-    const Dims& d = b.d;
-    if (d.nCellsSolve <= 0) continue;
-    Kessler a{};
-    a.nCellsSolve = d.nCellsSolve, a.nCells = d.nCells, a.K = d.K;
-    a.iqv = ctx->index_qv, a.iqc = ctx->mp_iqc, a.iqr = ctx->mp_iqr;
-    a.dt = dt, a.bucket = ctx->mp_bucket;
-    a.zz = P<const double>(ctx, b, "mesh", "zz");
-    a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
-    a.rho_zz = P<const double>(ctx, b, "state", "rho_zz", tl);
-    a.rtheta_base = P<const double>(ctx, b, "diag", "rtheta_base");
-    a.exner_base = P<const double>(ctx, b, "diag", "exner_base");
-    a.pressure_base = P<const double>(ctx, b, "diag", "pressure_base");
-    a.theta_m = P<double>(ctx, b, "state", "theta_m", tl);
-    a.scalars = P<double>(ctx, b, "state", "scalars", tl);
-    a.exner = P<double>(ctx, b, "diag", "exner");
-    a.rtheta_p = P<double>(ctx, b, "diag", "rtheta_p");
-    a.pressure_p = P<double>(ctx, b, "diag", "pressure_p");
-    a.rt_diabatic_tend = P<double>(ctx, b, "tend", "rt_diabatic_tend");
-    a.rainnc = P<double>(ctx, b, "diag_physics", "rainnc");
-    a.rainncv = P<double>(ctx, b, "diag_physics", "rainncv");
-    a.precipw = P<double>(ctx, b, "diag_physics", "precipw");
-    a.i_rainnc = P<int>(ctx, b, "diag_physics", "i_rainnc");
-    a.surface_pressure = P<double>(ctx, b, "diag", "surface_pressure");
-    a.tend_sfc_pressure = P<double>(ctx, b, "tend", "tend_sfc_pressure");
-    if (d.K > 64 * KESSLER_CHUNKS) {
-      ctx->err = "the Kessler kernel of this build holds at most " + std::to_string(64 * KESSLER_CHUNKS) + " levels";
-      return MPAS_DYC_EINVAL;
-    }
-    hipLaunchKernelGGL(k_kessler<KESSLER_CHUNKS>, dim3((unsigned)((d.nCellsSolve + KESSLER_WAVES - 1) / KESSLER_WAVES)),
-                       dim3(KESSLER_THREADS), 0, ctx->stream, a);
+    if (only && &b != only) continue;
+    for (auto& f : b.fields)
+      if (f.group == g && !f.buf[0]) CHK(alloc_field(ctx, b, f, true));
   }
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // zeroed before a set_field / get_field of the caller
   return MPAS_DYC_OK;
+}
+// every field of the group is allocated on every block: the buffers themselves say so
+bool group_ready(const mpas_dyc_ctx* ctx, Group g) {
+  for (const auto& b : ctx->blk)
+    for (const auto& f : b.fields)
+      if (f.group == g && !f.buf[0]) return false;
+  return true;
+}
+
+// enqueue() on the compute stream; under mpas_dyc_set_profile synchronously, between two events, with
+// the elapsed milliseconds left in `ms` (a measurement: the launches alone)
+template <class F>
+int timed_on_stream(mpas_dyc_ctx* ctx, double& ms, F enqueue) {
+  if (!ctx->profile) return enqueue();
+  for (auto& e : ctx->prof_step)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ctx->prof_step[0], ctx->stream));
+  const int r = enqueue();
+  HIPCHK(hipEventRecord(ctx->prof_step[1], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float t = 0.f;
+  (void)hipEventElapsedTime(&t, ctx->prof_step[0], ctx->prof_step[1]);
+  ms = t;
+  return r;
 }
 
 // Kernel families: 0 "general" (one column per wave, loads where used -- any mesh), 1 "batched"
@@ -952,6 +863,7 @@ int pack_mesh(mpas_dyc_ctx* ctx, Block& b) {
 // Halo-boundary flags of the split-phase exchanges: an edge is "boundary" when one of its
 // cells is a halo cell (it reads exchanged cell data); an owned cell is "boundary" when
 // one of its edges is a halo edge (it reads exchanged edge data).
+int convdiag_table(mpas_dyc_ctx* ctx, Block& b);  // physics_host.hip
 int compute_bnd(mpas_dyc_ctx* ctx) {
   for (auto& b : ctx->blk) {
     const Dims& d = b.d;
@@ -961,7 +873,7 @@ int compute_bnd(mpas_dyc_ctx* ctx) {
       return MPAS_DYC_ESTATE;
     }
     CHK(pack_mesh(ctx, b));
-    if (ctx->diag_alloc && !b.cv_ready) CHK(convdiag_table(ctx, b));
+    if (group_ready(ctx, G_CONVDIAG) && !b.cv.ready) CHK(convdiag_table(ctx, b));
     if (ctx->lbc && !pair_layout(d)) {
       ctx->err = lbc_layout_error(d);
       return MPAS_DYC_EINVAL;
@@ -1757,42 +1669,8 @@ int lbc_scalars(mpas_dyc_ctx* ctx, const std::vector<Ptrs>& P, double dt, double
   return MPAS_DYC_OK;
 }
 
-// atm_add_tend_anal_incr (mpas_atm_iau.F:81-217) of every block: physics + IAU into scratch.iau_*,
-// which P's tend_*_physics point at (make_ptrs), and into tend.scalars_tend in place.  Reads the
-// host's tend_physics arrays themselves (nullptr, read as 0.0, when the host supplies none).
-int iau_add_tend(mpas_dyc_ctx* ctx, const std::vector<Ptrs>& P) {
-  if (ctx->planning) return MPAS_DYC_OK;
-  const bool host_phys = (ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES) != 0;
-  for (size_t ib = 0; ib < ctx->blk.size(); ++ib) {
-    Block& b = ctx->blk[ib];
-    const Dims& d = b.d;
-    const Ptrs& p = P[ib];
-    const double* u_amb = (const double*)find(b, "tend_iau", "u")->buf[0];
-    const int64_t ne = (int64_t)(d.nEdges + 1) * d.K, nc = (int64_t)(d.nCells + 1) * d.K;
-    auto grid = [](int64_t n) {
-      return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + IAU_THREADS - 1) / IAU_THREADS, IAU_MAX_BLOCKS)));
-    };
-    hipLaunchKernelGGL(k_iau_edges, grid(ne / 2), dim3(IAU_THREADS), 0, ctx->stream, ne, (int64_t)d.nEdgesSolve * d.K,
-                       ctx->iau_wgt, (const double*)p.rho_edge, u_amb,
-                       host_phys ? ::P<const double>(ctx, b, "tend_physics", "tend_ru_physics") : nullptr, p.tend_ru_physics);
-    IauCells a{};
-    a.n = a.plane = nc;
-    a.n_solve = (int64_t)d.nCellsSolve * d.K;
-    a.ns = d.ns, a.moist_start = d.moist_start, a.moist_end = d.moist_end, a.index_qv = ctx->index_qv;
-    a.st_zero = host_phys ? 0 : 1;
-    a.wgt = ctx->iau_wgt;
-    a.zz = p.zz, a.rho_zz = p.rho_zz1, a.theta_m = p.theta_m1, a.scalars = p.scalars1;
-    a.rho_amb = (const double*)find(b, "tend_iau", "rho")->buf[0];
-    a.theta_amb = (const double*)find(b, "tend_iau", "theta")->buf[0];
-    a.scalars_amb = (const double*)find(b, "tend_iau", "scalars")->buf[0];
-    a.phys_rtheta = host_phys ? ::P<const double>(ctx, b, "tend_physics", "tend_rtheta_physics") : nullptr;
-    a.phys_rho = host_phys ? ::P<const double>(ctx, b, "tend_physics", "tend_rho_physics") : nullptr;
-    a.out_rtheta = p.tend_rtheta_physics, a.out_rho = p.tend_rho_physics, a.scalars_tend = p.scalars_tend;
-    if (nc & 1) hipLaunchKernelGGL(k_iau_cells<false>, grid(nc), dim3(IAU_THREADS), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k_iau_cells<true>, grid(nc / 2), dim3(IAU_THREADS), 0, ctx->stream, a);
-  }
-  return MPAS_DYC_OK;
-}
+// the step's physics hooks (IAU forcing, convective running maxima, device microphysics), host side
+#include "physics_host.hip"
 
 // The end of atm_srk3 after the microphysics (1650-1660): the regional reset of the specified
 // zone, "because microphysics has messed with them" (1672-1790), then summarize_timestep (1794) --
@@ -2183,7 +2061,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
                            dim3(256), 0, ctx->stream, ::P<double>(ctx, b, "state", "scalars", 2), n);
     }
     // 1650-1660: driver_microphysics on time level 2, when the device owns it (mpas_dyc_set_microphysics)
-    if (ctx->microp == MPAS_DYC_MICROP_KESSLER) CHK(kessler_enqueue(ctx, dt, 2));
+    if (ctx->microp.scheme == MPAS_DYC_MICROP_KESSLER) CHK(kessler_enqueue(ctx, dt, 2));
   }
   // the rest of the step follows the microphysics (1650-1660): when the host runs it, the host
   // calls mpas_dyc_finish_step after it
@@ -2366,13 +2244,9 @@ int profiled_step(mpas_dyc_ctx* ctx, double dt) {
     }
   };
   clear();
-  for (auto& e : ctx->prof_step)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(ctx->prof_step[0], ctx->stream));
   ctx->graph_ran = false;
-  const int r = srk3(ctx, dt);
-  HIPCHK(hipEventRecord(ctx->prof_step[1], ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  double tot = 0.0;
+  const int r = timed_on_stream(ctx, tot, [&]() -> int { return srk3(ctx, dt); });
   HIPCHK(hipStreamSynchronize(ctx->xstream));
   auto sum = [&](const std::vector<hipEvent_t>& v) {
     double ms = 0.0;
@@ -2382,8 +2256,6 @@ int profiled_step(mpas_dyc_ctx* ctx, double dt) {
     }
     return ms;
   };
-  float tot = 0.f;
-  (void)hipEventElapsedTime(&tot, ctx->prof_step[0], ctx->prof_step[1]);
   ctx->prof_out[0] = (double)(ctx->prof_exposed.size() / 2);
   ctx->prof_out[1] = tot;
   ctx->prof_out[2] = sum(ctx->prof_exposed);
@@ -2508,7 +2380,7 @@ int mpas_dyc_create_blocks(int32_t nblocks, const mpas_dyc_dims* dims, const mpa
   for (auto& b : ctx->blk) {
     build_registry(b);
     for (auto& f : b.fields) {
-      if (f.lazy) continue;
+      if (f.group != G_ALWAYS) continue;
       // 256 B of slack: the two-levels-per-lane kernels read 16 B at the last level of the last column
       const int64_t nb = field_bytes(b, f) + 256;
       for (int t = 0; t < f.ntl; ++t) {
@@ -2564,8 +2436,8 @@ void mpas_dyc_destroy(mpas_dyc_ctx* ctx) {
     }
     if (b.sum_part) (void)hipFree(b.sum_part);
     if (b.sum_out) (void)hipFree(b.sum_out);
-    if (b.cv_start) (void)hipFree(b.cv_start);
-    if (b.cv_kite) (void)hipFree(b.cv_kite);
+    if (b.cv.start) (void)hipFree(b.cv.start);
+    if (b.cv.kite) (void)hipFree(b.cv.kite);
   }
   if (ctx->sum_gather) (void)hipFree(ctx->sum_gather);
   p2p_teardown(ctx);  // after the plans (invalidate_plans above) and the field buffers: see there
@@ -2591,7 +2463,7 @@ int64_t mpas_dyc_block_field_bytes(const mpas_dyc_ctx* ctx, int32_t block, const
   auto it = b.by_name.find(std::string(pool) + "." + name);
   if (it == b.by_name.end()) return 0;
   const Field& f = b.fields[it->second];
-  if (is_microp(f) && !f.buf[0]) return 0;  // held only by a context that asked for them
+  if (GROUPS[f.group].hidden && !f.buf[0]) return 0;  // held only by a context that asked for them
   return field_bytes(b, f);
 }
 
@@ -2618,10 +2490,7 @@ void* mpas_dyc_field_device_ptr(mpas_dyc_ctx* ctx, const char* pool, const char*
 int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool, const char* name,
                              int32_t time_level, const void* host, int64_t nbytes) {
   if (!ctx || !pool || !name || !host) return MPAS_DYC_EINVAL;
-  if (ctx->host_only) {
-    ctx->err = "host-only context holds no fields";
-    return MPAS_DYC_ESTATE;
-  }
+  CHK(require_device(ctx));
   Block* bp = get_block(ctx, block);
   if (!bp) {
     ctx->err = "no block " + std::to_string(block);
@@ -2647,15 +2516,9 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
   }
   const int slot = slot_of(ctx, *f, time_level);
   HIPCHK(hipSetDevice(ctx->device));
-  if (f->lazy && !f->buf[slot] && is_convdiag(*f)) CHK(convdiag_alloc(ctx));  // all three, zeroed
-  if (f->lazy && !f->buf[slot] && is_microp(*f)) CHK(microp_alloc(ctx));      // all six, zeroed
-  if (f->lazy && !f->buf[slot]) {
-    HIPCHK(hipMalloc(&f->buf[slot], nb + 256));
-    if (f->pool == "tend_iau") {  // the pool is whole once one field is set: the others are zero until set
-      HIPCHK(hipMemset(f->buf[slot], 0, nb + 256));
-      CHK(iau_alloc(ctx, b, false));
-    }
-  }
+  if (!f->buf[slot])  // a G_ON_SET field alone, filled below; a hook's group whole: the others are zero until set
+    CHK(f->group == G_ON_SET ? alloc_field(ctx, b, *f, false)
+                             : alloc_group(ctx, f->group, GROUPS[f->group].all_blocks ? nullptr : &b));
   if (f->me) ctx->bnd_ready = false;  // pack_mesh copies the new image for the kernels
   if (f->is_int && f->target != T_NONE) {
     // MPAS 1-based -> device 0-based; out-of-range / 0 -> garbage slot
@@ -2680,8 +2543,8 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
     }
     if (f->pool == "mesh" && f->name == "cellsOnVertex") {  // the running maxima's table (convdiag_table)
       b.h_cov = tmp;
-      b.cv_ready = false;
-      if (ctx->diag_alloc) ctx->bnd_ready = false;
+      b.cv.ready = false;
+      if (group_ready(ctx, G_CONVDIAG)) ctx->bnd_ready = false;
     }
     if (f->pool == "mesh" && (f->name == "verticesOnEdge" || f->name == "edgesOnVertex")) {
       (f->name == "verticesOnEdge" ? b.h_voe : b.h_eov) = tmp;
@@ -2715,7 +2578,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
       const double* h = (const double*)host;
       int nz = 0;
       for (int64_t i = 0; i < nb / 8 && !nz; ++i) nz = h[i] != 0.0;
-      b.d.diabatic = nz || ctx->microp;  // the device microphysics writes it every step
+      b.d.diabatic = nz || ctx->microp.scheme;  // the device microphysics writes it every step
     }
   }
   return MPAS_DYC_OK;
@@ -2729,10 +2592,7 @@ int mpas_dyc_set_field(mpas_dyc_ctx* ctx, const char* pool, const char* name, in
 int mpas_dyc_get_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool, const char* name,
                              int32_t time_level, void* host, int64_t nbytes) {
   if (!ctx || !pool || !name || !host) return MPAS_DYC_EINVAL;
-  if (ctx->host_only) {
-    ctx->err = "host-only context holds no fields";
-    return MPAS_DYC_ESTATE;
-  }
+  CHK(require_device(ctx));
   Block* bp = get_block(ctx, block);
   if (!bp) {
     ctx->err = "no block " + std::to_string(block);
@@ -3141,216 +3001,6 @@ int mpas_dyc_set_lbc(mpas_dyc_ctx* ctx, int32_t apply, double seconds_to_interva
   return MPAS_DYC_OK;
 }
 
-int mpas_dyc_set_physics(mpas_dyc_ctx* ctx, int32_t flags) {
-  if (!ctx || (flags & ~(MPAS_DYC_PHYSICS_TENDENCIES | MPAS_DYC_PHYSICS_RQVDYNTEN | MPAS_DYC_PHYSICS_MICROPHYSICS)))
-    return MPAS_DYC_EINVAL;
-  if (ctx->host_only) return MPAS_DYC_ESTATE;
-  if ((flags & MPAS_DYC_PHYSICS_RQVDYNTEN) && !(flags & MPAS_DYC_PHYSICS_TENDENCIES)) return MPAS_DYC_EINVAL;
-  if ((flags & MPAS_DYC_PHYSICS_MICROPHYSICS) && ctx->microp) {
-    ctx->err = "MPAS_DYC_PHYSICS_MICROPHYSICS (the host's microphysics) with mpas_dyc_set_microphysics on";
-    return MPAS_DYC_ESTATE;
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->physics = flags;
-  for (auto& b : ctx->blk) b.d.physics = physics_tendencies(ctx) ? 1 : 0;
-  ctx->iau_stale = ctx->iau_on != 0;
-  drop_graphs(ctx);  // captured steps bake the flags in
-  return MPAS_DYC_OK;
-}
-
-int mpas_dyc_set_iau(mpas_dyc_ctx* ctx, int32_t on, double window_length_s) {
-  if (!ctx) return MPAS_DYC_EINVAL;
-  if (on && !(window_length_s > 0.0)) {
-    ctx->err = "mpas_dyc_set_iau: config_IAU_window_length_s must be positive";
-    return MPAS_DYC_EINVAL;
-  }
-  ctx->iau_on = on ? 1 : 0;
-  ctx->iau_window = on ? window_length_s : 0.0;
-  ctx->iau_wgt = 0.0;
-  if (ctx->host_only) return MPAS_DYC_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (auto& b : ctx->blk) {
-    if (on) CHK(iau_alloc(ctx, b, true));
-    b.d.physics = physics_tendencies(ctx) ? 1 : 0;
-  }
-  ctx->iau_stale = on != 0;
-  drop_graphs(ctx);  // captured steps bake the flag, the weight and the tendencies' pointers in
-  return MPAS_DYC_OK;
-}
-
-int mpas_dyc_iau_weight(const mpas_dyc_ctx* ctx, double dt, int32_t itimestep, double* wgt) {
-  if (!ctx || !wgt || !(dt > 0.0)) return MPAS_DYC_EINVAL;
-  *wgt = 0.0;
-  if (!ctx->iau_on) return MPAS_DYC_OK;
-  const long nsteps_iau = std::lround(ctx->iau_window / dt);  // nint: halves away from zero
-  if (itimestep <= nsteps_iau) *wgt = 1.0 / ctx->iau_window;
-  return MPAS_DYC_OK;
-}
-
-int mpas_dyc_set_diag_update(mpas_dyc_ctx* ctx, int32_t flags) {
-  if (!ctx) return MPAS_DYC_EINVAL;
-  if (flags & ~(CONVDIAG_W | CONVDIAG_WSP | CONVDIAG_UH)) {
-    ctx->err = "mpas_dyc_set_diag_update: unknown flag bits";
-    return MPAS_DYC_EINVAL;
-  }
-  ctx->diag_flags = flags;
-  if (ctx->host_only || !flags) return MPAS_DYC_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->diag_alloc) CHK(convdiag_alloc(ctx));
-  return MPAS_DYC_OK;
-}
-
-int mpas_dyc_diag_update(mpas_dyc_ctx* ctx) {
-  if (!ctx) return MPAS_DYC_EINVAL;
-  if (ctx->host_only) {
-    ctx->err = "host-only context holds no fields";
-    return MPAS_DYC_ESTATE;
-  }
-  if (ctx->tail_pending) {
-    ctx->err = "mpas_dyc_diag_update between mpas_dyc_timestep and mpas_dyc_finish_step";
-    return MPAS_DYC_ESTATE;
-  }
-  if (!ctx->diag_flags) return MPAS_DYC_OK;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (ctx->diag_flags & CONVDIAG_UH) {
-    if (!ctx->bnd_ready) CHK(compute_bnd(ctx));  // rebuilds the table after a new cellsOnVertex
-    for (auto& b : ctx->blk) {
-      if (!b.cv_ready) CHK(convdiag_table(ctx, b));
-      if (!find(b, "mesh", "areaCell")->buf[0]) {
-        ctx->err = "mpas_dyc_diag_update: mesh.areaCell not set (MPAS_DYC_DIAG_UPDRAFT_HELICITY_MAX divides by it)";
-        return MPAS_DYC_ESTATE;
-      }
-    }
-  }
-  if (ctx->profile) {
-    for (auto& e : ctx->prof_step)
-      if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventRecord(ctx->prof_step[0], ctx->stream));
-  }
-  for (auto& b : ctx->blk) {
-    const Dims& d = b.d;
-    if (d.nCellsSolve <= 0) continue;
-    ConvDiag a{};
-    a.nCellsSolve = d.nCellsSolve, a.K = d.K, a.flags = ctx->diag_flags;
-    a.w = P<const double>(ctx, b, "state", "w", 1);
-    a.vorticity = P<const double>(ctx, b, "diag", "vorticity");
-    a.uzonal = P<const double>(ctx, b, "diag", "uReconstructZonal");
-    a.umeridional = P<const double>(ctx, b, "diag", "uReconstructMeridional");
-    a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
-    a.areaCell = P<const double>(ctx, b, "mesh", "areaCell");
-    a.kiteAreasOnVertex = P<const double>(ctx, b, "mesh", "kiteAreasOnVertex");
-    a.cv_start = b.cv_start, a.cv_kite = b.cv_kite;
-    a.w_velocity_max = P<double>(ctx, b, "diag", CONVDIAG_FIELDS[0]);
-    a.wind_speed_level1_max = P<double>(ctx, b, "diag", CONVDIAG_FIELDS[1]);
-    a.updraft_helicity_max = P<double>(ctx, b, "diag", CONVDIAG_FIELDS[2]);
-    hipLaunchKernelGGL(k_convdiag, dim3((unsigned)((d.nCellsSolve + CONVDIAG_WAVES - 1) / CONVDIAG_WAVES)),
-                       dim3(CONVDIAG_THREADS), 0, ctx->stream, a);
-  }
-  HIPCHK(hipGetLastError());
-  if (ctx->profile) {  // measurement: synchronous, the launches between two events
-    float t = 0.f;
-    HIPCHK(hipEventRecord(ctx->prof_step[1], ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    (void)hipEventElapsedTime(&t, ctx->prof_step[0], ctx->prof_step[1]);
-    ctx->diag_ms = t;
-  }
-  return MPAS_DYC_OK;
-}
-
-int mpas_dyc_set_microphysics(mpas_dyc_ctx* ctx, int32_t scheme, int32_t index_qc, int32_t index_qr,
-                              double bucket_rainnc) {
-  if (!ctx) return MPAS_DYC_EINVAL;
-  if (scheme != MPAS_DYC_MICROP_OFF && scheme != MPAS_DYC_MICROP_KESSLER) {
-    ctx->err = "mpas_dyc_set_microphysics: unknown scheme";
-    return MPAS_DYC_EINVAL;
-  }
-  if (scheme != MPAS_DYC_MICROP_OFF) {
-    const int ns = ctx->blk.empty() ? 0 : ctx->blk[0].d.ns;
-    if (index_qc < 1 || index_qc > ns || index_qr < 1 || index_qr > ns || index_qc == index_qr ||
-        index_qc - 1 == ctx->index_qv || index_qr - 1 == ctx->index_qv) {
-      ctx->err = "mpas_dyc_set_microphysics: index_qc / index_qr must be distinct scalars in 1..num_scalars, not index_qv";
-      return MPAS_DYC_EINVAL;
-    }
-    if (ctx->physics & MPAS_DYC_PHYSICS_MICROPHYSICS) {
-      ctx->err = "mpas_dyc_set_microphysics with MPAS_DYC_PHYSICS_MICROPHYSICS (the host's microphysics) set";
-      return MPAS_DYC_ESTATE;
-    }
-    for (auto& b : ctx->blk)
-      if (b.d.K > 64 * KESSLER_CHUNKS) {
-        ctx->err = "the Kessler kernel of this build holds at most " + std::to_string(64 * KESSLER_CHUNKS) + " levels";
-        return MPAS_DYC_EINVAL;
-      }
-  }
-  if (!ctx->host_only) {
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (scheme != MPAS_DYC_MICROP_OFF && !ctx->mp_alloc) CHK(microp_alloc(ctx));
-  }
-  ctx->microp = scheme;
-  if (scheme != MPAS_DYC_MICROP_OFF) {
-    ctx->mp_iqc = index_qc - 1;
-    ctx->mp_iqr = index_qr - 1;
-    ctx->mp_bucket = bucket_rainnc;
-  }
-  for (auto& b : ctx->blk) {
-    b.d.physics = physics_tendencies(ctx) ? 1 : 0;
-    if (scheme != MPAS_DYC_MICROP_OFF) b.d.diabatic = 1;  // the step reads the scheme's rt_diabatic_tend
-  }
-  if (!ctx->host_only) drop_graphs(ctx);  // captured steps bake the switch, the indices and the bucket in
-  return MPAS_DYC_OK;
-}
-
-int mpas_dyc_microphysics(mpas_dyc_ctx* ctx, double dt, int32_t time_level) {
-  if (!ctx || !(dt > 0.0) || (time_level != 1 && time_level != 2)) return MPAS_DYC_EINVAL;
-  if (ctx->host_only) {
-    ctx->err = "host-only context holds no fields";
-    return MPAS_DYC_ESTATE;
-  }
-  if (ctx->microp == MPAS_DYC_MICROP_OFF) {
-    ctx->err = "mpas_dyc_microphysics: no scheme set (mpas_dyc_set_microphysics)";
-    return MPAS_DYC_ESTATE;
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  if (ctx->profile) {
-    for (auto& e : ctx->prof_step)
-      if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventRecord(ctx->prof_step[0], ctx->stream));
-  }
-  CHK(kessler_enqueue(ctx, dt, time_level));
-  HIPCHK(hipGetLastError());
-  if (ctx->profile) {  // measurement: synchronous, the launches between two events
-    float t = 0.f;
-    HIPCHK(hipEventRecord(ctx->prof_step[1], ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    (void)hipEventElapsedTime(&t, ctx->prof_step[0], ctx->prof_step[1]);
-    ctx->microp_ms = t;
-  }
-  return MPAS_DYC_OK;
-}
-
-int mpas_dyc_diag_reset(mpas_dyc_ctx* ctx, int32_t flags) {
-  if (!ctx) return MPAS_DYC_EINVAL;
-  if (flags & ~(CONVDIAG_W | CONVDIAG_WSP | CONVDIAG_UH)) {
-    ctx->err = "mpas_dyc_diag_reset: unknown flag bits";
-    return MPAS_DYC_EINVAL;
-  }
-  if (ctx->host_only) {
-    ctx->err = "host-only context holds no fields";
-    return MPAS_DYC_ESTATE;
-  }
-  if (!ctx->diag_alloc) return MPAS_DYC_OK;  // never allocated: zero when they are
-  HIPCHK(hipSetDevice(ctx->device));
-  for (auto& b : ctx->blk)
-    for (int i = 0; i < 3; ++i) {
-      if (!(flags & (1 << i))) continue;
-      Field* f = find(b, "diag", CONVDIAG_FIELDS[i]);
-      HIPCHK(hipMemsetAsync(f->buf[0], 0, field_bytes(b, *f), ctx->stream));
-    }
-  return MPAS_DYC_OK;
-}
-
 int mpas_dyc_model_init(mpas_dyc_ctx* ctx, int32_t h_scale_with_mesh, double config_zd, double config_xnutr) {
   if (!ctx) return MPAS_DYC_EINVAL;
   if (ctx->host_only) return MPAS_DYC_ESTATE;
@@ -3620,17 +3270,17 @@ int mpas_dyc_timestep(mpas_dyc_ctx* ctx, double dt, int32_t itimestep) {
   HIPCHK(hipSetDevice(ctx->device));
   // atm_iau_coef of this step (mpas_atm_iau.F:22-78): which of the two captured steps runs, never a
   // reason to capture again (the weight is the same for every forced step)
-  CHK(mpas_dyc_iau_weight(ctx, dt, itimestep, &ctx->iau_wgt));
+  CHK(mpas_dyc_iau_weight(ctx, dt, itimestep, &ctx->iau.wgt));
   if (iau_active(ctx)) {
-    ctx->iau_stale = true;
-  } else if (ctx->iau_on && ctx->iau_stale && !(ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES)) {
+    ctx->iau.stale = true;
+  } else if (ctx->iau.on && ctx->iau.stale && !(ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES)) {
     // an unforced step of a host that supplies no tendencies reads the library's arrays: zeros
     for (auto& b : ctx->blk)
       for (const char* n : {"scratch.iau_ru", "scratch.iau_rtheta", "scratch.iau_rho", "tend.scalars_tend"}) {
         Field& f = b.fields[b.by_name[n]];
         HIPCHK(hipMemsetAsync(f.buf[0], 0, field_bytes(b, f), ctx->stream));
       }
-    ctx->iau_stale = false;
+    ctx->iau.stale = false;
   }
   // a one-sided wait that timed out in an earlier step (its status word, copied back after every
   // step) fails this call, so a host that synchronises rarely does not step on with stale halos
@@ -3718,7 +3368,7 @@ int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on) {
 
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n) {
   if (!ctx || !out || n < 1) return MPAS_DYC_EINVAL;
-  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->diag_ms : i == 7 ? ctx->microp_ms : 0.0;
+  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : 0.0;
   return MPAS_DYC_OK;
 }
 

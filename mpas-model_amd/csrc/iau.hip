@@ -27,6 +27,16 @@ namespace mpas {
 constexpr int IAU_THREADS = 256;
 constexpr int IAU_MAX_BLOCKS = 2048;  // 8 workgroups per CU; the rest of the image by grid stride
 
+// The hook's host state (mpas_dyc_ctx::iau): config_IAU_option / _window_length_s, and atm_iau_coef of
+// the step being enqueued (> 1e-12: the step applies the forcing).  stale: the library's own
+// tendencies (scratch.iau_*, tend.scalars_tend of a host that supplies none) hold a forced step's
+// sums and are zeroed before the next unforced one reads them
+struct IauState {
+  int on = 0;
+  double window = 0.0, wgt = 0.0;
+  bool stale = false;
+};
+
 // tend_ru(k,i) = tend_ru(k,i) + wgt_iau * rho_edge(k,i) * u_amb(k,i)                      (170)
 __device__ __forceinline__ double iau_edge_term(double t, double wgt, double rho_edge, double u_amb) {
   return t + wgt * rho_edge * u_amb;

@@ -69,6 +69,14 @@ struct Kessler {
   int* i_rainnc;
 };
 
+// The hook's host state (mpas_dyc_ctx::microp): the MPAS_DYC_MICROP_* scheme of the step, the 0-based
+// scalar indices of cloud and rain water, config_bucket_rainnc, and the last mpas_dyc_microphysics
+// under mpas_dyc_set_profile (mpas_dyc_get_profile out[7])
+struct MicropState {
+  int scheme = 0, iqc = -1, iqr = -1;
+  double bucket = 0.0, ms = 0.0;
+};
+
 __device__ __forceinline__ double kessler_wave_max(double x) {
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) x = fmax(x, __shfl_xor(x, s, 64));

@@ -1,0 +1,313 @@
+// Host side of the step's physics hooks: the incremental analysis update (kernels: iau.hip), the
+// convective running maxima (convdiag.hip) and the device microphysics (kessler.hip).  Per hook: what
+// enqueues its kernels, and its entry points of include/mpas_dycore.h.  A hook's state struct
+// (mpas_dyc_ctx::iau / convdiag / microp, Block::cv) stands next to its kernels' argument struct; its
+// fields are a Group of the registry (dycore.hip build_registry), allocated by alloc_group.
+//
+// Included by dycore.hip inside its namespace, before srk3: after the structs (Field, Block,
+// mpas_dyc_ctx), HIPCHK / CHK, find, P, field_bytes, physics_tendencies, drop_graphs, require_device,
+// alloc_group, group_ready, timed_on_stream and compute_bnd.  The file closes that namespace for its
+// extern "C" entry points and opens it again at its end.
+
+// ---- incremental analysis update ----
+// atm_add_tend_anal_incr (mpas_atm_iau.F:81-217) of every block: physics + IAU into scratch.iau_*,
+// which P's tend_*_physics point at (make_ptrs), and into tend.scalars_tend in place.  Reads the
+// host's tend_physics arrays themselves (nullptr, read as 0.0, when the host supplies none).
+int iau_add_tend(mpas_dyc_ctx* ctx, const std::vector<Ptrs>& P) {
+  if (ctx->planning) return MPAS_DYC_OK;
+  const bool host_phys = (ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES) != 0;
+  for (size_t ib = 0; ib < ctx->blk.size(); ++ib) {
+    Block& b = ctx->blk[ib];
+    const Dims& d = b.d;
+    const Ptrs& p = P[ib];
+    const double* u_amb = (const double*)find(b, "tend_iau", "u")->buf[0];
+    const int64_t ne = (int64_t)(d.nEdges + 1) * d.K, nc = (int64_t)(d.nCells + 1) * d.K;
+    auto grid = [](int64_t n) {
+      return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + IAU_THREADS - 1) / IAU_THREADS, IAU_MAX_BLOCKS)));
+    };
+    hipLaunchKernelGGL(k_iau_edges, grid(ne / 2), dim3(IAU_THREADS), 0, ctx->stream, ne, (int64_t)d.nEdgesSolve * d.K,
+                       ctx->iau.wgt, (const double*)p.rho_edge, u_amb,
+                       host_phys ? ::P<const double>(ctx, b, "tend_physics", "tend_ru_physics") : nullptr, p.tend_ru_physics);
+    IauCells a{};
+    a.n = a.plane = nc;
+    a.n_solve = (int64_t)d.nCellsSolve * d.K;
+    a.ns = d.ns, a.moist_start = d.moist_start, a.moist_end = d.moist_end, a.index_qv = ctx->index_qv;
+    a.st_zero = host_phys ? 0 : 1;
+    a.wgt = ctx->iau.wgt;
+    a.zz = p.zz, a.rho_zz = p.rho_zz1, a.theta_m = p.theta_m1, a.scalars = p.scalars1;
+    a.rho_amb = (const double*)find(b, "tend_iau", "rho")->buf[0];
+    a.theta_amb = (const double*)find(b, "tend_iau", "theta")->buf[0];
+    a.scalars_amb = (const double*)find(b, "tend_iau", "scalars")->buf[0];
+    a.phys_rtheta = host_phys ? ::P<const double>(ctx, b, "tend_physics", "tend_rtheta_physics") : nullptr;
+    a.phys_rho = host_phys ? ::P<const double>(ctx, b, "tend_physics", "tend_rho_physics") : nullptr;
+    a.out_rtheta = p.tend_rtheta_physics, a.out_rho = p.tend_rho_physics, a.scalars_tend = p.scalars_tend;
+    if (nc & 1) hipLaunchKernelGGL(k_iau_cells<false>, grid(nc), dim3(IAU_THREADS), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(k_iau_cells<true>, grid(nc / 2), dim3(IAU_THREADS), 0, ctx->stream, a);
+  }
+  return MPAS_DYC_OK;
+}
+
+// ---- convective running maxima ----
+int convdiag_check_flags(mpas_dyc_ctx* ctx, int32_t flags, const char* entry) {
+  if (!(flags & ~(CONVDIAG_W | CONVDIAG_WSP | CONVDIAG_UH))) return MPAS_DYC_OK;
+  ctx->err = std::string(entry) + ": unknown flag bits";
+  return MPAS_DYC_EINVAL;
+}
+
+// The running maxima's derived table of one block: for each owned cell the (vertex, j) pairs with
+// cellsOnVertex(j, vertex) = cell, in ascending vertex index and then j -- the order in which the
+// reference's scatter over the vertices (convective_diagnostics.F:169-174) adds a cell's terms --
+// stored as 3 vertex + j.  Pairs of halo cells and of the garbage cell are dropped.  Rebuilt like
+// the other derived tables: setting cellsOnVertex clears cv.ready (and bnd_ready).
+int convdiag_table(mpas_dyc_ctx* ctx, Block& b) {
+  const Dims& d = b.d;
+  if ((int64_t)b.h_cov.size() < 3LL * d.nVertices) {
+    ctx->err = "mesh.cellsOnVertex not set";
+    return MPAS_DYC_ESTATE;
+  }
+  if (3LL * ((int64_t)d.nVertices + 1) > INT32_MAX) {
+    ctx->err = "too many vertices for the convective diagnostics' table";
+    return MPAS_DYC_EINVAL;
+  }
+  std::vector<int32_t> start((size_t)d.nCellsSolve + 1, 0);
+  for (int64_t i = 0; i < 3LL * d.nVertices; ++i)
+    if (b.h_cov[i] < d.nCellsSolve) ++start[b.h_cov[i] + 1];
+  for (int c = 0; c < d.nCellsSolve; ++c) start[c + 1] += start[c];
+  std::vector<int32_t> fill(start.begin(), start.end() - 1), kite((size_t)std::max(1, start[d.nCellsSolve]));
+  for (int64_t i = 0; i < 3LL * d.nVertices; ++i)  // ascending (vertex, j)
+    if (b.h_cov[i] < d.nCellsSolve) kite[fill[b.h_cov[i]]++] = (int32_t)i;
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // a running update still reads the old table
+  if (b.cv.start) (void)hipFree(b.cv.start);
+  if (b.cv.kite) (void)hipFree(b.cv.kite);
+  b.cv.start = b.cv.kite = nullptr;
+  HIPCHK(hipMalloc(&b.cv.start, start.size() * 4));
+  HIPCHK(hipMalloc(&b.cv.kite, kite.size() * 4));
+  HIPCHK(hipMemcpy(b.cv.start, start.data(), start.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b.cv.kite, kite.data(), kite.size() * 4, hipMemcpyHostToDevice));
+  b.cv.ready = true;
+  return MPAS_DYC_OK;
+}
+
+// convective_diagnostics_update with the context's mask on every block: one launch per block
+int convdiag_enqueue(mpas_dyc_ctx* ctx) {
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    if (d.nCellsSolve <= 0) continue;
+    ConvDiag a{};
+    a.nCellsSolve = d.nCellsSolve, a.K = d.K, a.flags = ctx->convdiag.flags;
+    a.w = P<const double>(ctx, b, "state", "w", 1);
+    a.vorticity = P<const double>(ctx, b, "diag", "vorticity");
+    a.uzonal = P<const double>(ctx, b, "diag", "uReconstructZonal");
+    a.umeridional = P<const double>(ctx, b, "diag", "uReconstructMeridional");
+    a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
+    a.areaCell = P<const double>(ctx, b, "mesh", "areaCell");
+    a.kiteAreasOnVertex = P<const double>(ctx, b, "mesh", "kiteAreasOnVertex");
+    a.cv_start = b.cv.start, a.cv_kite = b.cv.kite;
+    a.w_velocity_max = P<double>(ctx, b, "diag", CONVDIAG_FIELDS[0]);
+    a.wind_speed_level1_max = P<double>(ctx, b, "diag", CONVDIAG_FIELDS[1]);
+    a.updraft_helicity_max = P<double>(ctx, b, "diag", CONVDIAG_FIELDS[2]);
+    hipLaunchKernelGGL(k_convdiag, dim3((unsigned)((d.nCellsSolve + CONVDIAG_WAVES - 1) / CONVDIAG_WAVES)),
+                       dim3(CONVDIAG_THREADS), 0, ctx->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return MPAS_DYC_OK;
+}
+
+// ---- device microphysics ----
+// k_kessler<KESSLER_CHUNKS> holds a column of at most 64 levels per chunk
+int kessler_check_levels(mpas_dyc_ctx* ctx, int K) {
+  if (K <= 64 * KESSLER_CHUNKS) return MPAS_DYC_OK;
+  ctx->err = "the Kessler kernel of this build holds at most " + std::to_string(64 * KESSLER_CHUNKS) + " levels";
+  return MPAS_DYC_EINVAL;
+}
+
+// driver_microphysics for mp_kessler on time level tl of every block: one launch per block
+int kessler_enqueue(mpas_dyc_ctx* ctx, double dt, int tl) {
+  if (ctx->planning) return MPAS_DYC_OK;
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    if (d.nCellsSolve <= 0) continue;
+    Kessler a{};
+    a.nCellsSolve = d.nCellsSolve, a.nCells = d.nCells, a.K = d.K;
+    a.iqv = ctx->index_qv, a.iqc = ctx->microp.iqc, a.iqr = ctx->microp.iqr;
+    a.dt = dt, a.bucket = ctx->microp.bucket;
+    a.zz = P<const double>(ctx, b, "mesh", "zz");
+    a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
+    a.rho_zz = P<const double>(ctx, b, "state", "rho_zz", tl);
+    a.rtheta_base = P<const double>(ctx, b, "diag", "rtheta_base");
+    a.exner_base = P<const double>(ctx, b, "diag", "exner_base");
+    a.pressure_base = P<const double>(ctx, b, "diag", "pressure_base");
+    a.theta_m = P<double>(ctx, b, "state", "theta_m", tl);
+    a.scalars = P<double>(ctx, b, "state", "scalars", tl);
+    a.exner = P<double>(ctx, b, "diag", "exner");
+    a.rtheta_p = P<double>(ctx, b, "diag", "rtheta_p");
+    a.pressure_p = P<double>(ctx, b, "diag", "pressure_p");
+    a.rt_diabatic_tend = P<double>(ctx, b, "tend", "rt_diabatic_tend");
+    a.rainnc = P<double>(ctx, b, "diag_physics", "rainnc");
+    a.rainncv = P<double>(ctx, b, "diag_physics", "rainncv");
+    a.precipw = P<double>(ctx, b, "diag_physics", "precipw");
+    a.i_rainnc = P<int>(ctx, b, "diag_physics", "i_rainnc");
+    a.surface_pressure = P<double>(ctx, b, "diag", "surface_pressure");
+    a.tend_sfc_pressure = P<double>(ctx, b, "tend", "tend_sfc_pressure");
+    CHK(kessler_check_levels(ctx, d.K));
+    hipLaunchKernelGGL(k_kessler<KESSLER_CHUNKS>, dim3((unsigned)((d.nCellsSolve + KESSLER_WAVES - 1) / KESSLER_WAVES)),
+                       dim3(KESSLER_THREADS), 0, ctx->stream, a);
+  }
+  return MPAS_DYC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpas_dyc_set_physics(mpas_dyc_ctx* ctx, int32_t flags) {
+  if (!ctx || (flags & ~(MPAS_DYC_PHYSICS_TENDENCIES | MPAS_DYC_PHYSICS_RQVDYNTEN | MPAS_DYC_PHYSICS_MICROPHYSICS)))
+    return MPAS_DYC_EINVAL;
+  if (ctx->host_only) return MPAS_DYC_ESTATE;
+  if ((flags & MPAS_DYC_PHYSICS_RQVDYNTEN) && !(flags & MPAS_DYC_PHYSICS_TENDENCIES)) return MPAS_DYC_EINVAL;
+  if ((flags & MPAS_DYC_PHYSICS_MICROPHYSICS) && ctx->microp.scheme) {
+    ctx->err = "MPAS_DYC_PHYSICS_MICROPHYSICS (the host's microphysics) with mpas_dyc_set_microphysics on";
+    return MPAS_DYC_ESTATE;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->physics = flags;
+  for (auto& b : ctx->blk) b.d.physics = physics_tendencies(ctx) ? 1 : 0;
+  ctx->iau.stale = ctx->iau.on != 0;
+  drop_graphs(ctx);  // captured steps bake the flags in
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_set_iau(mpas_dyc_ctx* ctx, int32_t on, double window_length_s) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (on && !(window_length_s > 0.0)) {
+    ctx->err = "mpas_dyc_set_iau: config_IAU_window_length_s must be positive";
+    return MPAS_DYC_EINVAL;
+  }
+  ctx->iau.on = on ? 1 : 0;
+  ctx->iau.window = on ? window_length_s : 0.0;
+  ctx->iau.wgt = 0.0;
+  if (ctx->host_only) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (on)  // the increments a host has not set are zero; and the step's physics + IAU arrays
+    for (Group g : {G_IAU_INCR, G_IAU_SUMS}) CHK(alloc_group(ctx, g));
+  for (auto& b : ctx->blk) b.d.physics = physics_tendencies(ctx) ? 1 : 0;
+  ctx->iau.stale = on != 0;
+  drop_graphs(ctx);  // captured steps bake the flag, the weight and the tendencies' pointers in
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_iau_weight(const mpas_dyc_ctx* ctx, double dt, int32_t itimestep, double* wgt) {
+  if (!ctx || !wgt || !(dt > 0.0)) return MPAS_DYC_EINVAL;
+  *wgt = 0.0;
+  if (!ctx->iau.on) return MPAS_DYC_OK;
+  const long nsteps_iau = std::lround(ctx->iau.window / dt);  // nint: halves away from zero
+  if (itimestep <= nsteps_iau) *wgt = 1.0 / ctx->iau.window;
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_set_diag_update(mpas_dyc_ctx* ctx, int32_t flags) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  CHK(convdiag_check_flags(ctx, flags, "mpas_dyc_set_diag_update"));
+  ctx->convdiag.flags = flags;
+  if (ctx->host_only || !flags) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!group_ready(ctx, G_CONVDIAG)) CHK(alloc_group(ctx, G_CONVDIAG));
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_diag_update(mpas_dyc_ctx* ctx) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  CHK(require_device(ctx));
+  if (ctx->tail_pending) {
+    ctx->err = "mpas_dyc_diag_update between mpas_dyc_timestep and mpas_dyc_finish_step";
+    return MPAS_DYC_ESTATE;
+  }
+  if (!ctx->convdiag.flags) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (ctx->convdiag.flags & CONVDIAG_UH) {
+    if (!ctx->bnd_ready) CHK(compute_bnd(ctx));  // rebuilds the table after a new cellsOnVertex
+    for (auto& b : ctx->blk) {
+      if (!b.cv.ready) CHK(convdiag_table(ctx, b));
+      if (!find(b, "mesh", "areaCell")->buf[0]) {
+        ctx->err = "mpas_dyc_diag_update: mesh.areaCell not set (MPAS_DYC_DIAG_UPDRAFT_HELICITY_MAX divides by it)";
+        return MPAS_DYC_ESTATE;
+      }
+    }
+  }
+  return timed_on_stream(ctx, ctx->convdiag.ms, [&]() -> int { return convdiag_enqueue(ctx); });
+}
+
+int mpas_dyc_diag_reset(mpas_dyc_ctx* ctx, int32_t flags) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  CHK(convdiag_check_flags(ctx, flags, "mpas_dyc_diag_reset"));
+  CHK(require_device(ctx));
+  if (!group_ready(ctx, G_CONVDIAG)) return MPAS_DYC_OK;  // never allocated: zero when they are
+  HIPCHK(hipSetDevice(ctx->device));
+  for (auto& b : ctx->blk)
+    for (int i = 0; i < 3; ++i) {
+      if (!(flags & (1 << i))) continue;
+      Field* f = find(b, "diag", CONVDIAG_FIELDS[i]);
+      HIPCHK(hipMemsetAsync(f->buf[0], 0, field_bytes(b, *f), ctx->stream));
+    }
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_set_microphysics(mpas_dyc_ctx* ctx, int32_t scheme, int32_t index_qc, int32_t index_qr,
+                              double bucket_rainnc) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (scheme != MPAS_DYC_MICROP_OFF && scheme != MPAS_DYC_MICROP_KESSLER) {
+    ctx->err = "mpas_dyc_set_microphysics: unknown scheme";
+    return MPAS_DYC_EINVAL;
+  }
+  if (scheme != MPAS_DYC_MICROP_OFF) {
+    const int ns = ctx->blk.empty() ? 0 : ctx->blk[0].d.ns;
+    if (index_qc < 1 || index_qc > ns || index_qr < 1 || index_qr > ns || index_qc == index_qr ||
+        index_qc - 1 == ctx->index_qv || index_qr - 1 == ctx->index_qv) {
+      ctx->err = "mpas_dyc_set_microphysics: index_qc / index_qr must be distinct scalars in 1..num_scalars, not index_qv";
+      return MPAS_DYC_EINVAL;
+    }
+    if (ctx->physics & MPAS_DYC_PHYSICS_MICROPHYSICS) {
+      ctx->err = "mpas_dyc_set_microphysics with MPAS_DYC_PHYSICS_MICROPHYSICS (the host's microphysics) set";
+      return MPAS_DYC_ESTATE;
+    }
+    for (auto& b : ctx->blk) CHK(kessler_check_levels(ctx, b.d.K));
+  }
+  if (!ctx->host_only) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (scheme != MPAS_DYC_MICROP_OFF && !group_ready(ctx, G_MICROP)) CHK(alloc_group(ctx, G_MICROP));
+  }
+  ctx->microp.scheme = scheme;
+  if (scheme != MPAS_DYC_MICROP_OFF) {
+    ctx->microp.iqc = index_qc - 1;
+    ctx->microp.iqr = index_qr - 1;
+    ctx->microp.bucket = bucket_rainnc;
+  }
+  for (auto& b : ctx->blk) {
+    b.d.physics = physics_tendencies(ctx) ? 1 : 0;
+    if (scheme != MPAS_DYC_MICROP_OFF) b.d.diabatic = 1;  // the step reads the scheme's rt_diabatic_tend
+  }
+  if (!ctx->host_only) drop_graphs(ctx);  // captured steps bake the switch, the indices and the bucket in
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_microphysics(mpas_dyc_ctx* ctx, double dt, int32_t time_level) {
+  if (!ctx || !(dt > 0.0) || (time_level != 1 && time_level != 2)) return MPAS_DYC_EINVAL;
+  CHK(require_device(ctx));
+  if (ctx->microp.scheme == MPAS_DYC_MICROP_OFF) {
+    ctx->err = "mpas_dyc_microphysics: no scheme set (mpas_dyc_set_microphysics)";
+    return MPAS_DYC_ESTATE;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  return timed_on_stream(ctx, ctx->microp.ms, [&]() -> int {
+    CHK(kessler_enqueue(ctx, dt, time_level));
+    HIPCHK(hipGetLastError());
+    return MPAS_DYC_OK;
+  });
+}
+
+}  // extern "C"
+
+namespace {

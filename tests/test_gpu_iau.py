@@ -340,3 +340,41 @@ def test_iau_graph_branches():
             _same(_state(dy), eager[it - 1], f"graph, step {it}")
     dy.close()
     assert caps == [1, 2, 2, 3, 4, 4], caps
+
+
+def test_first_set_field_completes_the_pool_of_its_block_only():
+    """The tend_iau pool is allocated on demand, block by block: a first set of one of its fields
+    makes the other increments of that block readable, as zeros; the other block's pool stays
+    unallocated (MPAS_DYC_ESTATE on get) until set_iau(on), which completes every block's."""
+    import ctypes as C
+    from mpas_dycore import Dycore, decomp
+    case = _case(27, False)
+    blocks = decomp.decompose(case, decomp.partition_sfc(case["nCells"], 2))
+    assert not any(n in b.case for b in blocks for n in ("u_amb", "theta_amb", "rho_amb", "scalars_amb"))
+    dy = Dycore.from_blocks(blocks, device=0, moist_end=NS)
+    names = ("u", "theta", "rho", "scalars")
+
+    def rc_get(ib, n):
+        buf = np.empty(dy.field_bytes("tend_iau", n, block=ib) // 8)
+        assert buf.size > 0
+        return dy.lib.mpas_dyc_get_block_field(dy.h, ib, b"tend_iau", n.encode(), 1, buf.ctypes.data_as(C.c_void_p),
+                                               buf.nbytes)
+
+    assert all(rc_get(ib, n) == -3 for ib in (0, 1) for n in names)   # MPAS_DYC_ESTATE: nothing set yet
+    K = case["nVertLevels"]
+    u1 = np.random.default_rng(11).standard_normal((blocks[1].case["nEdges"] + 1) * K)
+    dy.set_raw("tend_iau", "u", u1, block=1)
+    assert np.array_equal(dy.get_raw("tend_iau", "u", block=1), u1)
+    for n, size in (("theta", K), ("rho", K), ("scalars", K * NS)):
+        a = dy.get_raw("tend_iau", n, block=1)
+        assert a.shape == ((blocks[1].case["nCells"] + 1) * size,) and not a.any(), n
+    assert all(rc_get(0, n) == -3 for n in names)                     # block 0 is as it was
+    dy.set_iau(True, _window(case)[1])
+    for ib in (0, 1):
+        for n in names:
+            a = dy.get_raw("tend_iau", n, block=ib)
+            if (ib, n) == (1, "u"):
+                assert np.array_equal(a, u1)
+            else:
+                assert a.size and not a.any(), (ib, n)
+    dy.close()
