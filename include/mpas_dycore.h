@@ -580,7 +580,16 @@ int mpas_dyc_fused_tend_acoustic(mpas_dyc_ctx* ctx);
  * at most 63 levels, no vertical mixing of u; MPAS_DYCORE_FOLD_RK1_EDGES=0 turns it off);
  * bit 2 = the w recovery after a stage runs in the launch of the diagnostics' cell kernel
  * (k_recover3_diag_cells_b; split transport, one block without exchanges or LBCs, the pair layout,
- * at most 63 levels; MPAS_DYCORE_FUSE_RECOVER_DIAG=0 turns it off).
+ * at most 63 levels; MPAS_DYCORE_FUSE_RECOVER_DIAG=0 turns it off); bit 3 = the recoveries of
+ * stages 1 and 2 store no ruAvg / wwAvg: the next stage forms both again without reading them, and
+ * the transport and the substep averaging read stage 3's (the conditions of bit 0;
+ * MPAS_DYCORE_SKIP_STAGE_AVG=0 turns it off); bit 4 = the acoustic cell phases form cofwr, a_tri
+ * and gamma_tri in registers from the other coefficients, and of a dt's coefficient calls only the
+ * last stores the three (every block count, LBC runs too; at most 63 levels, maxEdges 6 or 7).  Set
+ * while the coefficient arrays are those of the context's last coefficient call: not before the
+ * first step, and not after mpas_dyc_set_field / mpas_dyc_field_device_ptr of coftz, cofwz, cofwr,
+ * cofwt, a_tri, alpha_tri, gamma_tri or cofrz, until the next step (MPAS_DYCORE_DERIVE_COEFS=0 turns
+ * it off).
  * 0 = none.  Valid once the mesh is set. */
 int mpas_dyc_folded_passes(mpas_dyc_ctx* ctx);
 

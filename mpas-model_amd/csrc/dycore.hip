@@ -254,6 +254,16 @@ struct mpas_dyc_ctx {
   // the substep averaging of ruAvg / wwAvg in stage 3's last damping and cell phase
   // (substep_avg_folded); MPAS_DYCORE_FOLD_SUBSTEP_AVG=0: k_substep_finish_v
   bool fold_substep_avg = true;
+  // stages 1 and 2 store no ruAvg / wwAvg where nothing reads them (stage_avg_skipped);
+  // MPAS_DYCORE_SKIP_STAGE_AVG=0: every stage stores them
+  bool skip_stage_avg = true;
+  // the acoustic cell phases form cofwr, a_tri and gamma_tri in registers and the coefficient calls
+  // but the dt's last do not store them (coefs_derived); MPAS_DYCORE_DERIVE_COEFS=0: stored and loaded
+  bool derive_coefs = true;
+  // the coefficient arrays are those of this context's last vert_imp_coefs call, whose dtseps was
+  // vic_dtseps: set there, cleared by any set or device-pointer hand-over of one of them (coefs_touched)
+  bool vic_own = false;
+  double vic_dtseps = 0.0;
   // rk 1's del4 term and final tend_u in k_dyn_edges_p (rk1_edge_folded);
   // MPAS_DYCORE_FOLD_RK1_EDGES=0: k_dyn_edges_rk1b_b
   bool fold_rk1_edges = true;
@@ -1053,20 +1063,47 @@ void rk_integration_setup(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p) {
 }
 
 
-void vert_imp_coefs(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dts) {
+// The record kernels fuse the owned cells' recover_cells1 into a stage's last sub-step
+bool fused_recover(const Dims& d) { return batched(d) && (d.maxEdges == 6 || d.maxEdges == 7); }
+
+// Whether block d's acoustic cell phases (the record kernels) form cofwr, a_tri and gamma_tri from
+// the other coefficients instead of loading them (acoustic_cells_col with DRV): only while the
+// arrays are what this context's last coefficient call computed, by the kernels that share the
+// expressions (not k_vert_imp_lu's split form).  The 64-lane build only.
+bool coefs_derived(const mpas_dyc_ctx* ctx, const Dims& d) {
+#ifdef MPAS_WIDE
+  return false;
+#else
+  return ctx->derive_coefs && ctx->vic_own && g_vic != 2 && fused_recover(d);
+#endif
+}
+// a set or a device-pointer hand-over of a coefficient array: it may no longer be this context's own
+void coefs_touched(mpas_dyc_ctx* ctx, const Field& f) {
+  if (f.pool != "diag") return;
+  for (const char* n : {"coftz", "cofwz", "cofwr", "cofwt", "a_tri", "alpha_tri", "gamma_tri", "cofrz"})
+    if (f.name == n) ctx->vic_own = false;
+}
+
+// last = 0: not the dt's last call.  A block whose cell phases derive cofwr, a_tri and gamma_tri
+// then stores none of the three (k_vert_imp_coefs_p's store_drv); the dt's last call stores all, so
+// the pool holds after a step what it held with every call storing them.
+void vert_imp_coefs(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dts, bool last = true) {
+  if (!ctx->planning) {  // a planning pass launches nothing
+    ctx->vic_own = true;
+    ctx->vic_dtseps = .5 * dts * (1. + ctx->cf.epssm);  // the kernels' dtseps
+  }
+  const int store_drv = (last || !coefs_derived(ctx, d)) ? 1 : 0;
   if (g_vic == 2) {  // coefficients per column, then the LU chains one lane per column
     LAUNCH(k_vert_imp_coefs<true>, std::max(d.nCellsSolve, 1), d, p, dts, ctx->cf.epssm);
     if (d.nCellsSolve > 0 && !ctx->planning)
       hipLaunchKernelGGL(k_vert_imp_lu, dim3((unsigned)((d.nCellsSolve + 63) / 64)), dim3(64), 0, ctx->stream, d, p);
   } else if (pair_layout(d) && g_vic == 1) {
-    LAUNCH_PE((k_vert_imp_coefs_p<false>), (k_vert_imp_coefs_p<true>), std::max(d.nCellsSolve, 1), d, p, dts, ctx->cf.epssm);
+    LAUNCH_PE((k_vert_imp_coefs_p<false>), (k_vert_imp_coefs_p<true>), std::max(d.nCellsSolve, 1), d, p, dts, ctx->cf.epssm,
+              store_drv);
   } else {
     LAUNCH(k_vert_imp_coefs<false>, std::max(d.nCellsSolve, 1), d, p, dts, ctx->cf.epssm);
   }
 }
-
-// The record kernels fuse the owned cells' recover_cells1 into a stage's last sub-step
-bool fused_recover(const Dims& d) { return batched(d) && (d.maxEdges == 6 || d.maxEdges == 7); }
 
 // A stage's first acoustic cell phase as dyn_tend launches it with its last cell kernel
 // (k_dyn_cells3_acoustic_r): the cell phase's pointers (stage_fin at rk 1) and arguments
@@ -1077,6 +1114,7 @@ struct TendAcoustic {
   int keep_pp, dl, store_tend;
   int sa;         // the substep averaging of wwAvg in the fused recovery (substep_avg_folded), or 0
   double sa_inv;
+  bool drv;       // the cell phase derives cofwr, a_tri and gamma_tri (coefs_derived)
 };
 // Whether stage rk_step of nsub sub-steps runs that launch: nothing lies between the two kernels
 // (no exchange, so no cell with a halo edge is left to k_smlstep_pert_b; no LBC kernels), both are
@@ -1101,6 +1139,22 @@ bool substep_avg_folded(const mpas_dyc_ctx* ctx) {
   return false;
 #else
   if (!ctx->fold_substep_avg || needs_exchange(ctx) || ctx->lbc || ctx->blk.size() != 1) return false;
+  if (!ctx->cf.split_dynamics_transport) return false;
+  const Dims& d = ctx->blk[0].d;
+  return pair_layout(d) && fused_recover(d) && d.nCellsSolve == d.nCells && d.nEdgesSolve == d.nEdges &&
+         d.n_bnd_edges == 0;
+#endif
+}
+// Whether the recoveries of stages 1 and 2 skip their stores of ruAvg / wwAvg (SA_SKIP in
+// kernels.hip).  The next stage forms ruAvg afresh from dts * tend_u and its sub-step 1 zeroes wwAvg
+// without reading it; the other readers must be out of the way: the transport outside the dynamics
+// (it sees stage 3's values, as does the substep averaging, folded or not), no exchange, no LBC,
+// and the recovering kernels must be the only writers left (the conditions of substep_avg_folded).
+bool stage_avg_skipped(const mpas_dyc_ctx* ctx) {
+#ifdef MPAS_WIDE
+  return false;
+#else
+  if (!ctx->skip_stage_avg || needs_exchange(ctx) || ctx->lbc || ctx->blk.size() != 1) return false;
   if (!ctx->cf.split_dynamics_transport) return false;
   const Dims& d = ctx->blk[0].d;
   return pair_layout(d) && fused_recover(d) && d.nCellsSolve == d.nCells && d.nEdgesSolve == d.nEdges &&
@@ -1246,8 +1300,17 @@ void dyn_tend(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, int rk_step, doub
     // rho_zz2_rd / theta_m2_rd are this stage's ru / rw / w2 / rho_zz2 / theta_m2, which the
     // tendencies read
     const TendAcArgs a{ta->dts, cf.epssm, ta->rdt, ta->invNs, rk_step, ta->keep_pp, ta->dl,
-                       ta->store_tend, ta->sa, ta->sa_inv};
+                       ta->store_tend, ta->sa, ta->sa_inv, ctx->vic_dtseps};
     const bool m6 = d.maxEdges == 6, fin = ta->fin;
+    if (ta->drv) {
+      if (m6 && rk_step == 1) LAUNCH((k_dyn_cells3_acoustic_r<6, true, true, AC_DRV>), d.nCells, d, ta->pf, cf, s, a);
+      if (m6 && rk_step != 1 && fin) LAUNCH((k_dyn_cells3_acoustic_r<6, false, true, AC_DRV>), d.nCells, d, ta->pf, cf, s, a);
+      if (m6 && rk_step != 1 && !fin) LAUNCH((k_dyn_cells3_acoustic_r<6, false, false, AC_DRV>), d.nCells, d, ta->pf, cf, s, a);
+      if (!m6 && rk_step == 1) LAUNCH((k_dyn_cells3_acoustic_r<7, true, true, AC_DRV>), d.nCells, d, ta->pf, cf, s, a);
+      if (!m6 && rk_step != 1 && fin) LAUNCH((k_dyn_cells3_acoustic_r<7, false, true, AC_DRV>), d.nCells, d, ta->pf, cf, s, a);
+      if (!m6 && rk_step != 1 && !fin) LAUNCH((k_dyn_cells3_acoustic_r<7, false, false, AC_DRV>), d.nCells, d, ta->pf, cf, s, a);
+      return;
+    }
     if (m6 && rk_step == 1) LAUNCH((k_dyn_cells3_acoustic_r<6, true, true>), d.nCells, d, ta->pf, cf, s, a);
     if (m6 && rk_step != 1 && fin) LAUNCH((k_dyn_cells3_acoustic_r<6, false, true>), d.nCells, d, ta->pf, cf, s, a);
     if (m6 && rk_step != 1 && !fin) LAUNCH((k_dyn_cells3_acoustic_r<6, false, false>), d.nCells, d, ta->pf, cf, s, a);
@@ -1331,6 +1394,25 @@ void acoustic_edges(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dts,
 void acoustic_cells(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double dts, int small_step, int fin = 0,
                     double rdt = 0.0, double invNs = 0.0, int rk_step = 0, int keep_pp = 1, PackMap pk = PackMap{},
                     int dl = 0, XPack rp = XPack{}, int sa = 0, double sa_inv = 0.0) {
+#ifndef MPAS_WIDE
+  if (coefs_derived(ctx, d)) {  // cofwr, a_tri and gamma_tri formed in registers, from vic_dtseps
+    const double cds = ctx->vic_dtseps, eps = ctx->cf.epssm;
+    const bool m6 = d.maxEdges == 6;
+    if (m6 && fin)
+      LAUNCH((k_acoustic_cells_r<6, true, AC_DRV>), d.nCells, d, p, dts, small_step, eps, rdt, invNs, rk_step, keep_pp, pk, dl,
+             rp, sa, sa_inv, cds);
+    else if (m6)
+      LAUNCH((k_acoustic_cells_r<6, false, AC_DRV>), d.nCells, d, p, dts, small_step, eps, 0.0, 0.0, 0, 1, pk, 0, XPack{}, 0,
+             0.0, cds);
+    else if (fin)
+      LAUNCH((k_acoustic_cells_r<7, true, AC_DRV>), d.nCells, d, p, dts, small_step, eps, rdt, invNs, rk_step, keep_pp, pk, dl,
+             rp, sa, sa_inv, cds);
+    else
+      LAUNCH((k_acoustic_cells_r<7, false, AC_DRV>), d.nCells, d, p, dts, small_step, eps, 0.0, 0.0, 0, 1, pk, 0, XPack{}, 0,
+             0.0, cds);
+    return;
+  }
+#endif
   if (batched(d) && d.maxEdges == 6) {
     if (fin)
       LAUNCH((k_acoustic_cells_r<6, true>), d.nCells, d, p, dts, small_step, ctx->cf.epssm, rdt, invNs, rk_step, keep_pp,
@@ -1766,12 +1848,16 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
   }
   if (ctx->overlap_all) sml_fused = false, rec_overlap = true;
   const bool avg_folded = substep_avg_folded(ctx);
+  const bool avg_skipped = stage_avg_skipped(ctx);
   const bool rd_fused = recover_diag_fused(ctx);
-  EACHV(Ppre, vert_imp_coefs(ctx, d, p, rk_sub_timestep[0]));    // 476-510 of dynamics substep 1
+  // the dt's last coefficient call (it alone stores the arrays the cell phases derive, vert_imp_coefs):
+  // order 3: rk 2 of the last dynamics substep; order 2: the last substep's start
+  const bool o3 = cf.time_integration_order == 3;
+  EACHV(Ppre, vert_imp_coefs(ctx, d, p, rk_sub_timestep[0], !o3 && dynamics_split == 1));  // 476-510 of dynamics substep 1
   for (int dynamics_substep = 1; dynamics_substep <= dynamics_split; ++dynamics_substep) {
     // 513 (exner): carried by the step-start exchange and by the 1282-1297 exchange below
     for (int rk_step = 1; rk_step <= 3; ++rk_step) {
-      if (cf.time_integration_order == 3 && rk_step == 2) EACH(vert_imp_coefs(ctx, d, p, rk_sub_timestep[1]));
+      if (o3 && rk_step == 2) EACH(vert_imp_coefs(ctx, d, p, rk_sub_timestep[1], dynamics_substep == dynamics_split));
       const bool last_stage = dynamics_substep == dynamics_split && rk_step == 3;
       const bool hdiv_next = !lbc && rk_step < 3 && (!split || (rk_step == 1 && cf.time_integration_order == 3));
       // the first stage reads time level 2 and the saved fields through stage_pre until its recovery
@@ -1789,15 +1875,16 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
       // tend_theta are stored for a second sub-step or, after the dt's last stage, for the pool)
       const bool fuse_ta = tend_acoustic_fused(ctx, rk_step, nsub);
       // stage 3's last damping and cell phase average ruAvg / wwAvg over the dynamics substeps
+      // stages 1 and 2: their ruAvg / wwAvg have no reader and are not stored (stage_avg_skipped)
       const int sa = (avg_folded && rk_step == 3)
                          ? SA_ON | (dynamics_substep == 1 ? SA_FIRST : 0) | (dynamics_substep == dynamics_split ? SA_LAST : 0)
-                         : 0;
+                         : (avg_skipped && rk_step < 3) ? SA_SKIP : 0;
       const double sa_inv = 1.0 / (double)dynamics_split;
       TendAcoustic ta{};
       if (fuse_ta)
         ta = TendAcoustic{PF[0], nsub == 1, dts, rk_timestep[rk_step - 1], 1 / (double)nsub, last_stage ? 1 : 0,
                           nsub == 1 ? damping_delta(ctx, ctx->blk[0].d, last_stage) : 0, (nsub > 1 || last_stage) ? 1 : 0,
-                          nsub == 1 ? sa : 0, sa_inv};
+                          nsub == 1 ? sa : 0, sa_inv, coefs_derived(ctx, ctx->blk[0].d)};
       const TendAcoustic* tap = fuse_ta ? &ta : nullptr;
       if (pending) {  // 561-630, k_dyn_cells1 overlapping the exchange
         EACHV(PS, dyn_tend(ctx, d, p, rk_step, dt, 1, hdiv_prev && batched(d)));
@@ -1987,7 +2074,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
         if (rk_step == 3 && dynamics_substep < dynamics_split) {
           CHK((exchange)(ctx, {{"state", "theta_m", 2, ALL_LAYERS}, {"diag", "pressure_p", 0, ALL_LAYERS},
                                {"diag", "rtheta_p", 0, ALL_LAYERS}, {"diag", "exner", 0, ALL_LAYERS}}));
-          EACH(vert_imp_coefs(ctx, d, p, rk_sub_timestep[0]));     // 476-510 of the next substep
+          EACH(vert_imp_coefs(ctx, d, p, rk_sub_timestep[0], !o3 && dynamics_substep + 1 == dynamics_split));  // 476-510 of the next substep
         }
       } else if (rk_step < 3) {
         CHK(xchg(xd));  // waited for inside the next stage's dyn_tend
@@ -2000,7 +2087,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
         xd.insert(xd.end(), {{"state", "theta_m", 2, ALL_LAYERS}, {"diag", "pressure_p", 0, ALL_LAYERS},
                              {"diag", "rtheta_p", 0, ALL_LAYERS}, {"diag", "exner", 0, ALL_LAYERS}});
         CHK(xchg(xd));
-        EACH(vert_imp_coefs(ctx, d, p, rk_sub_timestep[0]));     // 476-510 of the next substep
+        EACH(vert_imp_coefs(ctx, d, p, rk_sub_timestep[0], !o3 && dynamics_substep + 1 == dynamics_split));  // 476-510 of the next substep
         CHK(xwait());
       } else if (split) {
         // the dt's last 1234-1249: overlaps substep_finish, which reads and writes none of its
@@ -2374,6 +2461,8 @@ int mpas_dyc_create_blocks(int32_t nblocks, const mpas_dyc_dims* dims, const mpa
   if (const char* oa = getenv("MPAS_DYCORE_OVERLAP_ALL")) ctx->overlap_all = std::string(oa) == "1";
   if (const char* ft = getenv("MPAS_DYCORE_FUSE_TEND_ACOUSTIC")) ctx->fuse_tend_acoustic = std::string(ft) != "0";
   if (const char* fs = getenv("MPAS_DYCORE_FOLD_SUBSTEP_AVG")) ctx->fold_substep_avg = std::string(fs) != "0";
+  if (const char* dc = getenv("MPAS_DYCORE_DERIVE_COEFS")) ctx->derive_coefs = std::string(dc) != "0";
+  if (const char* ss = getenv("MPAS_DYCORE_SKIP_STAGE_AVG")) ctx->skip_stage_avg = std::string(ss) != "0";
   if (const char* fe = getenv("MPAS_DYCORE_FOLD_RK1_EDGES")) ctx->fold_rk1_edges = std::string(fe) != "0";
   if (const char* fr = getenv("MPAS_DYCORE_FUSE_RECOVER_DIAG")) ctx->fuse_recover_diag = std::string(fr) != "0";
   if (const char* ov = getenv("MPAS_DYCORE_OVERLAP")) ctx->overlap = std::atoi(ov);
@@ -2480,6 +2569,7 @@ void* mpas_dyc_block_field_device_ptr(mpas_dyc_ctx* ctx, int32_t block, const ch
   // the kernels read packed copies of the maxEdges-strided mesh fields (pack_mesh) and zb_cell / zb3_cell
   // through zb_p / zb_m: a caller may write through the pointer, so the next step packs them again
   if (f->me || (f->pool == "mesh" && (f->name == "zb_cell" || f->name == "zb3_cell"))) ctx->bnd_ready = false;
+  coefs_touched(ctx, *f);
   return f->buf[slot_of(ctx, *f, time_level)];
 }
 
@@ -2520,6 +2610,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
     CHK(f->group == G_ON_SET ? alloc_field(ctx, b, *f, false)
                              : alloc_group(ctx, f->group, GROUPS[f->group].all_blocks ? nullptr : &b));
   if (f->me) ctx->bnd_ready = false;  // pack_mesh copies the new image for the kernels
+  coefs_touched(ctx, *f);
   if (f->is_int && f->target != T_NONE) {
     // MPAS 1-based -> device 0-based; out-of-range / 0 -> garbage slot
     const int64_t n = field_elems(b, *f);
@@ -3522,6 +3613,10 @@ int mpas_dyc_folded_passes(mpas_dyc_ctx* ctx) {
   for (const auto& b : ctx->blk) all = all && rk1_edge_folded(ctx, b.d);
   if (all) m |= 2;
   if (recover_diag_fused(ctx)) m |= 4;
+  if (stage_avg_skipped(ctx)) m |= 8;
+  bool drv = !ctx->blk.empty();
+  for (const auto& b : ctx->blk) drv = drv && coefs_derived(ctx, b.d);
+  if (drv) m |= 16;
   return m;
 }
 

@@ -459,6 +459,22 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_moist_edges(Dims d, Ptrs p) {
 // ============================================================================
 // atm_compute_vert_imp_coefs_work  (mpas_atm_time_integration.F:2064-2129)
 // ============================================================================
+// cofwr (2079) and the a and c of the tridiagonal system (2108-2121) of levels k >= 1, as functions
+// of their operands (m: level k-1, p: level k+1; rz = cofrz = dtseps * rdzw): the kernels below call
+// them, and so do the acoustic cell phases that form cofwr, a_tri and gamma_tri = c * alpha_tri in
+// registers instead of loading them (acoustic_cells_col with DRV) -- the same expression trees on the
+// same operands, without contraction, so the same doubles.  The callers apply the level masks.
+__device__ __forceinline__ double vic_cofwr(double dtseps, double fzm, double fzp, double zz, double zzm) {
+  return .5 * dtseps * GRAVITY * (fzm * zz + fzp * zzm);
+}
+__device__ __forceinline__ double vic_a(double wz, double wr, double wtm, double tzm, double rwm, double zm,
+                                        double rzm) {
+  return -wz * tzm * rwm * zm + wr * rzm - wtm * tzm * rwm;
+}
+__device__ __forceinline__ double vic_c(double wz, double wr, double wt, double tzp, double rw, double z, double rz) {
+  return -wz * tzp * rw * z - wr * rz + wt * tzp * rw;
+}
+
 // SPLIT (the builds of more than 128 lanes): the column's LU recurrence is left to k_vert_imp_lu, one
 // lane per column; this kernel stores b and c of the tridiagonal system in alpha_tri / gamma_tri
 template <bool SPLIT = false>
@@ -481,7 +497,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_vert_imp_coefs(Dims d, Ptrs p
   const double zzm = up1(zz), pm = up1(pp), tm = up1(t);
   double cofwr = 0.0, cofwz = 0.0, coftz = 0.0;
   if (act && k >= 1) {
-    cofwr = .5 * dtseps * GRAVITY * (fzm * zz + fzp * zzm);
+    cofwr = vic_cofwr(dtseps, fzm, fzp, zz, zzm);
     cofwz = dtseps * c2 * (fzm * zz + fzp * zzm) * rdzu * cqw * (fzm * pp + fzp * pm);
     coftz = dtseps * (fzm * t + fzp * tm);
   }
@@ -493,10 +509,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_vert_imp_coefs(Dims d, Ptrs p
   const double cofrz = dtseps * rdzw, cofrz_m = up1(cofrz);
   double a = 0.0, b = 1.0, cc = 0.0;
   if (act && k >= 1) {
-    a = -cofwz * coftz_m * rdzw_m * zzm + cofwr * cofrz_m - cofwt_m * coftz_m * rdzw_m;
+    a = vic_a(cofwz, cofwr, cofwt_m, coftz_m, rdzw_m, zzm, cofrz_m);
     b = 1. + cofwz * (coftz * rdzw * zz + coftz * rdzw_m * zzm) - coftz * (cofwt * rdzw - cofwt_m * rdzw_m) +
         cofwr * (cofrz - cofrz_m);
-    cc = -cofwz * coftz_p * rdzw * zz - cofwr * cofrz + cofwt * coftz_p * rdzw;
+    cc = vic_c(cofwz, cofwr, cofwt, coftz_p, rdzw, zz, cofrz);
   }
   // sequential LU recurrence in the reference order (2124-2127)
   double alpha = 0.0, gamma = 0.0;
@@ -2906,8 +2922,12 @@ __device__ __forceinline__ d2 ld_pp(const Dims& d, const Ptrs& p, const UnpackMa
 // launches no k_substep_finish_v.  A substep that is not the last stores no ruAvg / wwAvg at all:
 // the next stage forms ruAvg afresh from dts * tend_u and sub-step 1 zeroes wwAvg.
 // sa: 0 = off (store `a` as before); else SA_ON | SA_FIRST for substep 1 | SA_LAST for the last one
-enum { SA_ON = 1, SA_FIRST = 2, SA_LAST = 4 };
+// SA_SKIP (alone): nothing is stored.  Stages 1 and 2 of a block for which srk3 finds no reader
+// (stage_avg_skipped): the next stage forms ruAvg afresh from dts * tend_u and its sub-step 1 zeroes
+// wwAvg without reading it; the transport and the substep averaging see stage 3's values.
+enum { SA_ON = 1, SA_FIRST = 2, SA_LAST = 4, SA_SKIP = 8 };
 __device__ __forceinline__ void store_avg(double* avg, double* split, size_t i, double a, int sa, double inv) {
+  if (sa & SA_SKIP) return;
   if (!sa) {
     avg[i] = a;
     return;
@@ -2919,7 +2939,7 @@ __device__ __forceinline__ void store_avg(double* avg, double* split, size_t i, 
 
 // dl = 1: rtheta_pp_old holds rtheta_pp - rtheta_pp_old (k_acoustic_cells_r<ME, true> with dl)
 // rp: the stage's last damping also packs ru_p of the 876-887 exchange (XPack), or nothing
-// sa, sa_inv (REC only): the substep averaging of ruAvg on the recovered edges (store_avg)
+// sa, sa_inv (REC only): the substep averaging of ruAvg on the recovered edges, or SA_SKIP (store_avg)
 template <bool REC = false, bool UP = false, bool ODD = false>
 __global__ __launch_bounds__(PAIR_THREADS) void k_divdamp_p(Dims d, Ptrs p, double coef_divdamp, int phase, double dts,
                                                             int fresh, double invNs = 0.0, UnpackMap um = UnpackMap{},
@@ -2978,7 +2998,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_divdamp_p(Dims d, Ptrs p, doub
   const bool rB = onB && (phase ? bB : p.edge_bnd[eB]) == 0;
   const d2 rs = ld2(p.ru_save + o);
   const d2 ra = fresh ? ru : ld2(p.ruAvg + o);  // fresh: sub-step 1 left ruAvg = dts * tend_u
-  const d2 sp = (sa && !(sa & SA_FIRST)) ? ld2(p.ruAvg_split + o) : d2{0.0, 0.0};
+  const d2 sp = ((sa & SA_ON) && !(sa & SA_FIRST)) ? ld2(p.ruAvg_split + o) : d2{0.0, 0.0};
   const d2 z1 = ld2(p.rho_zz2 + o1), z2 = ld2(p.rho_zz2 + o2);
   const d2 rr{rs.x + out.x, rs.y + out.y};
   const d2 un{2. * rr.x / (z1.x + z2.x), 2. * rr.y / (z1.y + z2.y)};
@@ -2989,7 +3009,8 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_divdamp_p(Dims d, Ptrs p, doub
     if (!(dl && (h ? rB : rA))) pst(p.ru_p + o, out, two);
     if (h ? rB : rA) {  // recover_edges (3048-3059), same expressions
       const d2 av{rs.x + (ra.x * invNs), rs.y + (ra.y * invNs)};
-      if (!sa) {
+      if (sa & SA_SKIP) {  // no reader before the next stage's sub-step 1 (store_avg)
+      } else if (!sa) {
         pst(p.ruAvg + o, av, two);
       } else {  // store_avg on the pair
         const d2 s2 = (sa & SA_FIRST) ? av : d2{av.x + sp.x, av.y + sp.y};
@@ -3230,8 +3251,12 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_mono_edges1_p(Dims d, Ptrs p, 
 // runs as a lane-shift sweep: each iteration finalizes one more lane (two levels, the second from
 // the first in registers), K/2 iterations instead of K-1, each from exactly the operands of the
 // sequential recurrence -- and a wave now carries two columns, halving the DP work per column.
+// store_drv = 0: cofwr, a_tri and gamma_tri are not stored.  Every cell phase until the next call
+// forms them in registers (acoustic_cells_col with DRV); srk3 passes 1 for the dt's last call, so
+// the pool holds after a step what it held with every call storing them.
 template <bool ODD = false>
-__global__ __launch_bounds__(PAIR_THREADS) void k_vert_imp_coefs_p(Dims d, Ptrs p, double dts, double epssm) {
+__global__ __launch_bounds__(PAIR_THREADS) void k_vert_imp_coefs_p(Dims d, Ptrs p, double dts, double epssm,
+                                                                   int store_drv = 1) {
   const int K = d.K, h = pair_half(), l = pair_lane();
   const double dtseps = .5 * dts * (1. + epssm);
   const double rcv = RGAS / (CP - RGAS);
@@ -3264,7 +3289,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_vert_imp_coefs_p(Dims d, Ptrs 
   auto lev1 = [&](bool act, int k, double zz_, double zzm_, double pp_, double pm_, double t_, double tm_,
                   double fzm_, double fzp_, double rdzu_, double cqw_, double& wr, double& wz, double& tz) {
     if (act && k >= 1) {
-      wr = .5 * dtseps * GRAVITY * (fzm_ * zz_ + fzp_ * zzm_);
+      wr = vic_cofwr(dtseps, fzm_, fzp_, zz_, zzm_);
       wz = dtseps * c2 * (fzm_ * zz_ + fzp_ * zzm_) * rdzu_ * cqw_ * (fzm_ * pp_ + fzp_ * pm_);
       tz = dtseps * (fzm_ * t_ + fzp_ * tm_);
     }
@@ -3281,9 +3306,9 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_vert_imp_coefs_p(Dims d, Ptrs 
                   double tzm, double tzp, double wtm, double rw, double rwm, double z, double zm, double rz,
                   double rzm) {
     if (act && k >= 1) {
-      a_ = -wz * tzm * rwm * zm + wr * rzm - wtm * tzm * rwm;
+      a_ = vic_a(wz, wr, wtm, tzm, rwm, zm, rzm);
       b_ = 1. + wz * (tz * rw * z + tz * rwm * zm) - tz * (wt * rw - wtm * rwm) + wr * (rz - rzm);
-      c_ = -wz * tzp * rw * z - wr * rz + wt * tzp * rw;
+      c_ = vic_c(wz, wr, wt, tzp, rw, z, rz);
     }
   };
   lev2(ax, kx, a.x, b.x, cc.x, cofwz.x, cofwr.x, cofwt.x, coftz.x, coftz_m.x, coftz_p.x, cofwt_m.x, rdzw.x,
@@ -3306,16 +3331,18 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_vert_imp_coefs_p(Dims d, Ptrs 
   }
   if (mine && ax) {
     if (l == 0) {  // level 1 only: cofwr(1) / cofwz(1) are not written (2077-2081)
-      p.cofwr[o + 1] = cofwr.y;
+      if (store_drv) p.cofwr[o + 1] = cofwr.y;
       p.cofwz[o + 1] = cofwz.y;
     } else {
-      pst(p.cofwr + o, cofwr, two);
+      if (store_drv) pst(p.cofwr + o, cofwr, two);
       pst(p.cofwz + o, cofwz, two);
     }
     pst(p.cofwt + o, cofwt, two);
-    pst(p.a_tri + o, a, two);
     pst(p.alpha_tri + o, alpha, two);
-    pst(p.gamma_tri + o, gamma, two);
+    if (store_drv) {
+      pst(p.a_tri + o, a, two);
+      pst(p.gamma_tri + o, gamma, two);
+    }
   }
   // coftz(1) = coftz(K+1) = 0: levels 0..K, the lane holding level K stores that one level
   if (mine && kx <= K) {
@@ -3532,19 +3559,29 @@ struct AcIn {
   double rz, dss, rws, rw, w2, cofrz, rdzw, fzm, fzp;
 };
 // the operands that only the cell phase reads: tend_rho and the coefficients of atm_compute_vert_imp_coefs
-template <int ME>
+// DRV (bits 1 / 2 / 4: cofwr / a_tri / gamma_tri): not loaded, acoustic_cells_col forms it
+template <int ME, int DRV = 0>
 __device__ __forceinline__ void load_ac_own(const Ptrs& p, size_t o, size_t ow, int kc, AcIn<ME>& in) {
   in.trho = p.tend_rho[o];
-  in.coftz = p.coftz[ow], in.cofwt = p.cofwt[o], in.cofwz = p.cofwz[o], in.cofwr = p.cofwr[o];
-  in.a_tri = p.a_tri[o], in.alpha_tri = p.alpha_tri[o], in.gamma_tri = p.gamma_tri[o];
+  in.coftz = p.coftz[ow], in.cofwt = p.cofwt[o], in.cofwz = p.cofwz[o], in.alpha_tri = p.alpha_tri[o];
+  in.cofwr = (DRV & 1) ? 0.0 : p.cofwr[o];
+  in.a_tri = (DRV & 2) ? 0.0 : p.a_tri[o];
+  in.gamma_tri = (DRV & 4) ? 0.0 : p.gamma_tri[o];
   in.dss = p.dss[o];
   in.cofrz = p.cofrz[kc];
 }
-template <int ME, bool FIN>
+// DRV (bits 1 / 2 / 4; the 64-lane build): cofwr / a_tri / gamma_tri are formed here by the
+// functions the coefficient kernels call (vic_cofwr, vic_a, vic_c) from operands the column holds
+// anyway, instead of being loaded: three streams fewer here and in k_vert_imp_coefs_p (store_drv).
+// cdtseps is the dtseps of the context's last coefficient call -- inside srk3 that of this dts, in
+// mpas_dyc_time_acoustic_step not necessarily.  The host picks these forms only while the
+// coefficient arrays are the context's own (coefs_derived in dycore.hip).
+constexpr int AC_DRV = 7;  // what the deriving forms derive
+template <int ME, bool FIN, int DRV = 0>
 __device__ __forceinline__ void acoustic_cells_col(const Dims& d, const Ptrs& p, int c, const AcIn<ME>& in, double dts,
                                                    int small_step, double epssm, double rdt, double invNs, int rk_step,
                                                    int keep_pp, const PackMap& pk, int dl, const XPack& rp, int sa = 0,
-                                                   double sa_inv = 0.0) {
+                                                   double sa_inv = 0.0, double cdtseps = 0.0) {
   const int k = lane_id(), K = d.K;
   const bool act = k < K, actw = k <= K;
   const int kc = min(k, K - 1), kw = min(k, K);
@@ -3554,8 +3591,8 @@ __device__ __forceinline__ void acoustic_cells_col(const Dims& d, const Ptrs& p,
   const double invA = in.invA, spec = in.spec;
   double rtpp = in.rtpp, rhopp = in.rhopp, rwp = in.rwp, wwa = in.wwa;
   const double thc = in.thc, trho = in.trho, tth = in.tth, tw = in.tw;
-  const double coftz = in.coftz, zz = in.zz, cofwt = in.cofwt, cofwz = in.cofwz, cofwr = in.cofwr;
-  const double a_tri = in.a_tri, alpha_tri = in.alpha_tri, gamma_tri = in.gamma_tri;
+  const double coftz = in.coftz, zz = in.zz, cofwt = in.cofwt, cofwz = in.cofwz, alpha_tri = in.alpha_tri;
+  double cofwr = in.cofwr, a_tri = in.a_tri, gamma_tri = in.gamma_tri;
   const double rz = in.rz, dss = in.dss, rws = in.rws, rw = in.rw, w2 = in.w2;
   const double cofrz = in.cofrz, rdzw = in.rdzw, fzm = in.fzm, fzp = in.fzp;
   RecIn ri{};
@@ -3585,10 +3622,18 @@ __device__ __forceinline__ void acoustic_cells_col(const Dims& d, const Ptrs& p,
     double up7[7] = {zz, ts, rs, rtpp, rhopp, cofwt, rz};  // levels k-1
     col_shift(up7, -1);
     const double zzm = up7[0], tsm = up7[1], rsm = up7[2], rtppm = up7[3], rhoppm = up7[4], cofwtm = up7[5];
+    if (DRV & 1) cofwr = (act && k >= 1) ? vic_cofwr(cdtseps, fzm, fzp, zz, zzm) : 0.0;
     if (act && k >= 1) {
       rwp = rwp + dts * tw - cofwz * ((zz * ts - zzm * tsm) + resm * (zz * rtpp - zzm * rtppm)) -
             cofwr * ((rs + rsm) + resm * (rhopp + rhoppm)) + cofwt * (ts + resm * rtpp) +
             cofwtm * (tsm + resm * rtppm);
+    }
+    if (DRV & 6) {  // a and c of levels k >= 1 as the coefficient kernels form them; 0 at level 0
+      const double coftz_m = up1(coftz), rdzw_m = up1(rdzw);
+      if (DRV & 2)
+        a_tri = (act && k >= 1) ? vic_a(cofwz, cofwr, cofwtm, coftz_m, rdzw_m, zzm, cdtseps * rdzw_m) : 0.0;
+      if (DRV & 4)
+        gamma_tri = (act && k >= 1) ? vic_c(cofwz, cofwr, cofwt, coftz_p, rdzw, zz, cdtseps * rdzw) * alpha_tri : 0.0;
     }
     // tridiagonal solve sweeping up and then down the column (2675-2682), reference order
 #ifdef MPAS_WIDE
@@ -3662,12 +3707,14 @@ __device__ __forceinline__ void acoustic_cells_col(const Dims& d, const Ptrs& p,
 #else
 #define ACOUSTIC_CELLS_ATTR
 #endif
-template <int ME, bool FIN = false>
+// DRV, cdtseps: see acoustic_cells_col
+template <int ME, bool FIN = false, int DRV = 0>
 __global__ __launch_bounds__(BLOCK_THREADS) ACOUSTIC_CELLS_ATTR void k_acoustic_cells_r(Dims d, Ptrs p, double dts, int small_step,
                                                                     double epssm, double rdt = 0.0,
                                                                     double invNs = 0.0, int rk_step = 0,
                                                                     int keep_pp = 1, PackMap pk = PackMap{}, int dl = 0,
-                                                                    XPack rp = XPack{}, int sa = 0, double sa_inv = 0.0) {
+                                                                    XPack rp = XPack{}, int sa = 0, double sa_inv = 0.0,
+                                                                    double cdtseps = 0.0) {
   const int c = wave_elem(0);
   if (c >= d.nCells) return;
   const int k = lane_id(), K = d.K;
@@ -3710,13 +3757,16 @@ __global__ __launch_bounds__(BLOCK_THREADS) ACOUSTIC_CELLS_ATTR void k_acoustic_
 #pragma unroll
     for (int i = 0; i < ME; ++i) in.ru[i] = dts * in.ru[i];
   }
-  in.coftz = p.coftz[ow], in.zz = p.zz[o], in.cofwt = p.cofwt[o], in.cofwz = p.cofwz[o], in.cofwr = p.cofwr[o];
-  in.a_tri = p.a_tri[o], in.alpha_tri = p.alpha_tri[o], in.gamma_tri = p.gamma_tri[o];
+  in.coftz = p.coftz[ow], in.zz = p.zz[o], in.cofwt = p.cofwt[o], in.cofwz = p.cofwz[o], in.alpha_tri = p.alpha_tri[o];
+  in.cofwr = (DRV & 1) ? 0.0 : p.cofwr[o];
+  in.a_tri = (DRV & 2) ? 0.0 : p.a_tri[o];
+  in.gamma_tri = (DRV & 4) ? 0.0 : p.gamma_tri[o];
   // rho_zz (tl2), rw and w (tl2) through the *_rd pointers: in a dynamics substep's first stage
   // they name the buffers that hold these values until the recovery (srk3, stage_fin)
   in.rz = p.rho_zz2_rd[o], in.dss = p.dss[o], in.rws = p.rw_save[ow], in.rw = p.rw_rd[ow], in.w2 = p.w2_rd[ow];
   in.cofrz = p.cofrz[kc], in.rdzw = p.rdzw[kc], in.fzm = p.fzm[kc], in.fzp = p.fzp[kc];
-  acoustic_cells_col<ME, FIN>(d, p, c, in, dts, small_step, epssm, rdt, invNs, rk_step, keep_pp, pk, dl, rp, sa, sa_inv);
+  acoustic_cells_col<ME, FIN, DRV>(d, p, c, in, dts, small_step, epssm, rdt, invNs, rk_step, keep_pp, pk, dl, rp, sa,
+                                   sa_inv, cdtseps);
 }
 
 #ifndef MPAS_WIDE
@@ -3739,8 +3789,9 @@ struct TendAcArgs {
   int rk_step, keep_pp, dl, store_tend;
   int sa;
   double sa_inv;
+  double cdtseps;  // DRV forms: the dtseps of the last coefficient call (acoustic_cells_col)
 };
-template <int ME, bool RK1, bool FIN>
+template <int ME, bool RK1, bool FIN, int DRV = 0>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_acoustic_r(Dims d, Ptrs p, Config cf, DynTendScal s,
                                                                          TendAcArgs a) {
   const int c = wave_elem(0);
@@ -3758,7 +3809,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_acoustic_r(Dims d,
   AcIn<ME> in;
   // the cell phase's own operands after the tendencies' gathers have been consumed: with them they
   // would be live across the whole tendency part
-  load_ac_own(p, o, ow, kc, in);
+  load_ac_own<ME, DRV>(p, o, ow, kc, in);
   // rk 1's tendencies do not read theta_m (time level 1) across the edges; gathered here and not
   // with the tendencies' loads, the rk 1 form (ME = 6) needs 157 VGPRs instead of 169: 3 waves per
   // SIMD instead of 2 (at 2 it ran slower than the two kernels)
@@ -3779,8 +3830,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_dyn_cells3_acoustic_r(Dims d,
   }
   in.zz = cy.zz, in.rz = cy.rz, in.rws = cy.rws, in.rw = cy.rw, in.w2 = cy.w2;
   in.rdzw = cy.rdzw, in.fzm = cy.fzm, in.fzp = cy.fzp;
-  acoustic_cells_col<ME, FIN>(d, p, c, in, a.dts, 1, a.epssm, a.rdt, a.invNs, a.rk_step, a.keep_pp, PackMap{}, a.dl,
-                              XPack{}, a.sa, a.sa_inv);
+  acoustic_cells_col<ME, FIN, DRV>(d, p, c, in, a.dts, 1, a.epssm, a.rdt, a.invNs, a.rk_step, a.keep_pp, PackMap{}, a.dl,
+                                   XPack{}, a.sa, a.sa_inv, a.cdtseps);
 }
 #endif
 

@@ -583,9 +583,16 @@ class Dycore:
         (MPAS_DYCORE_FOLD_SUBSTEP_AVG=0: off); "rk1_edges" -- stage 1's edge kernel applies the del4
         term and forms the final tend_u and k_dyn_edges_rk1b_b is not launched
         (MPAS_DYCORE_FOLD_RK1_EDGES=0: off); "recover_diag" -- the w recovery runs in the launch of the
-        diagnostics' cell kernel (MPAS_DYCORE_FUSE_RECOVER_DIAG=0: off).  () when none applies."""
+        diagnostics' cell kernel (MPAS_DYCORE_FUSE_RECOVER_DIAG=0: off); "stage_avg_stores" -- the
+        recoveries of stages 1 and 2 store no ruAvg / wwAvg, which nothing reads before the next stage
+        forms them again (MPAS_DYCORE_SKIP_STAGE_AVG=0: off); "derived_coefs" -- the acoustic cell phases
+        form cofwr, a_tri and gamma_tri in registers and only the dt's last coefficient call stores
+        them: reported while the coefficient arrays are those of this context's last coefficient call,
+        so not before the first step and not after a set of one of them
+        (MPAS_DYCORE_DERIVE_COEFS=0: off).  () when none applies."""
         m = int(self.lib.mpas_dyc_folded_passes(self.h))
-        return tuple(n for i, n in enumerate(("substep_avg", "rk1_edges", "recover_diag")) if m & (1 << i))
+        names = ("substep_avg", "rk1_edges", "recover_diag", "stage_avg_stores", "derived_coefs")
+        return tuple(n for i, n in enumerate(names) if m & (1 << i))
 
     def exchange_profile(self, dt: float, itimestep: int = 1) -> dict:
         """One eager atm_timestep with HIP events around every exchange's exposed part and every

@@ -82,6 +82,10 @@ VARIANT = {
                                                            "theta_m2", "w2"}},
     "k_divdamp_p<true": {},
     "k_acoustic_edges_p<true": {},
+    # the deriving forms (DRV = 7) form cofwr, a_tri and gamma_tri in registers, on top of the rules above
+    **{f"{k}<6, {v}, 7": {"drop": {"cofwr", "a_tri", "gamma_tri"}}
+       for k, vs in (("k_acoustic_cells_r", ("false", "true")),
+                     ("k_dyn_cells3_acoustic_r", ("true, true", "false, true", "false, false"))) for v in vs},
     "k_diag_edges_p": {"drop_w": {"gradPVn", "gradPVt"}},
 }
 EXTRA_READS = {  # pointer arguments, not Ptrs members
