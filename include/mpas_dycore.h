@@ -589,7 +589,12 @@ int mpas_dyc_fused_tend_acoustic(mpas_dyc_ctx* ctx);
  * while the coefficient arrays are those of the context's last coefficient call: not before the
  * first step, and not after mpas_dyc_set_field / mpas_dyc_field_device_ptr of coftz, cofwz, cofwr,
  * cofwt, a_tri, alpha_tri, gamma_tri or cofrz, until the next step (MPAS_DYCORE_DERIVE_COEFS=0 turns
- * it off).
+ * it off); bit 5 = the diagnostics' cell kernel forms vorticity, ke_vertex and pv_vertex of the
+ * cell's vertices itself from u at the cell's edges and spokes and stores pv_vertex and vorticity,
+ * k_diag_vertices_p is not launched and ke_vertex is not stored (one block without exchanges whose
+ * cells are all owned, the pair layout, at most 63 levels, and a mesh on which every vertex slot i
+ * of a cell touches the cell's edges i and i-1 and every vertex has three cells;
+ * MPAS_DYCORE_FUSE_DIAG_VERTICES=0 turns it off).
  * 0 = none.  Valid once the mesh is set. */
 int mpas_dyc_folded_passes(mpas_dyc_ctx* ctx);
 

@@ -110,6 +110,16 @@ struct Ptrs {
   // one scalar load.
   const int* cell_rec;
   const double* cell_sdv;
+  // per-cell vertex records (k_build_vtx_rec), for the cell kernels that form their vertices'
+  // diagnostics themselves (diag_cells_vtx_col).  vtx_rec = VTX_REC int32 per cell: [3 i + j] =
+  // edgesOnVertex(j) of the vertex in slot i (verticesOnCell(i)): the cell's own edges i and i-1 (mod
+  // nEdgesOnCell) and the spoke, the edge between the two neighbouring cells; [21] bit i = this cell
+  // is the vertex's cellsOnVertex(1) and stores it.  vtx_coef = VTX_COEF doubles per (cell, slot),
+  // maxEdges slots per cell: [0, 3) edgesOnVertex_sign * dcEdge and [3, 6) dcEdge * dvEdge in
+  // edgesOnVertex order, [6] invAreaTriangle, [7] fVertex, [8] dcEdge * dvEdge of own edge i, [9] the
+  // slot's kiteAreasOnVertex; unused slots -> garbage edge and 0.
+  const int* vtx_rec;
+  const double* vtx_coef;
   // ---- regional LBCs (lbc.hip): zone masks, relaxation scaling, the driving data of the lbc pool
   // (_t = tendency, lbc_<field> time level 1; _s = interval-end state, time level 2), the seconds
   // from the step start to the interval end, and the scalar filter's scratch
@@ -121,6 +131,7 @@ struct Ptrs {
   double* lbc_tmp;
 };
 constexpr int CELL_REC = 16, CELL_REC_ME = 7;
+constexpr int VTX_REC = 24, VTX_COEF = 10;
 
 // Halo pack fused into a producer (the acoustic cell phase, k_acoustic_cells_r): owned cell c of the
 // block writes its new rtheta_pp (and rho_pp) column also to rt[s] (rho[s]) for s in

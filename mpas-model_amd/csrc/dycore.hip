@@ -112,6 +112,9 @@ struct Block {
   // h_eoc use these strides).  d.maxEdges / d.maxEdges2 are the strides the kernels index with:
   // max(nEdgesOnCell) and the edgesOnEdge slots the kernels need after pack_mesh
   int me_decl = 0, me2_decl = 0;
+  // every element passed the checks of the per-cell vertex records (k_build_vtx_rec,
+  // k_check_vtx_writers; compute_bnd)
+  bool vtx_ok = false;
   // summarize_timestep records (summary.hip): partials and one SUM_REC record per field
   double* sum_part = nullptr;
   double* sum_out = nullptr;
@@ -270,6 +273,10 @@ struct mpas_dyc_ctx {
   // the w recovery and the diagnostics' cell kernel in one launch (k_recover3_diag_cells_b,
   // recover_diag_fused); MPAS_DYCORE_FUSE_RECOVER_DIAG=0: the two kernels
   bool fuse_recover_diag = true;
+  // the diagnostics' cell kernel forms vorticity, ke_vertex and pv_vertex of its vertices itself and
+  // k_diag_vertices_p is not launched (diag_vertices_fused); MPAS_DYCORE_FUSE_DIAG_VERTICES=0: the
+  // vertex kernel
+  bool fuse_diag_vertices = true;
   std::vector<XField> late_fs;
   bool late_pending = false;
   bool fused_pack_enabled = true;       // MPAS_DYCORE_FUSED_PACK=0: pack kernel instead (A/B)
@@ -491,6 +498,8 @@ void build_registry(Block& c) {
   add(c, "scratch", "bnd_cells", L_CELL, 1, 1, true);
   add(c, "scratch", "cell_rec", L_CELL, CELL_REC, 1, true);
   add(c, "scratch", "cell_sdv", L_CELL, ME);
+  add(c, "scratch", "vtx_rec", L_CELL, VTX_REC, 1, true);
+  add(c, "scratch", "vtx_coef", L_CELL, (int64_t)ME * VTX_COEF);
   add(c, "scratch", "zb_p", L_CELL, (int64_t)ME * (K + 1));
   add(c, "scratch", "zb_m", L_CELL, (int64_t)ME * (K + 1));
   // the saves srk3 rotates instead of copying (rotate_saves)
@@ -543,6 +552,16 @@ void build_registry(Block& c) {
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
     c.fields[c.by_name[std::string("mesh.") + n]].me = 1;
   for (const char* n : {"edgesOnEdge", "weightsOnEdge"}) c.fields[c.by_name[std::string("mesh.") + n]].me = 2;
+}
+
+// A mesh field that the per-cell records copy values of (compute_bnd: cell_sdv, vtx_rec, vtx_coef)
+// without being maxEdges-strided: a new image means new records
+bool rec_input(const Field& f) {
+  if (f.pool != "mesh") return false;
+  for (const char* n : {"dcEdge", "dvEdge", "edgesOnVertex", "cellsOnVertex", "edgesOnVertex_sign", "invAreaTriangle",
+                        "fVertex", "kiteAreasOnVertex"})
+    if (f.name == n) return true;
+  return false;
 }
 
 Field* find(Block& b, const char* pool, const char* name) {
@@ -639,6 +658,8 @@ Ptrs make_ptrs(mpas_dyc_ctx* c, Block& b) {
   p.bnd_cells = P<const int>(c, b, "scratch", "bnd_cells");
   p.cell_rec = P<const int>(c, b, "scratch", "cell_rec");
   p.cell_sdv = P<const double>(c, b, "scratch", "cell_sdv");
+  p.vtx_rec = P<const int>(c, b, "scratch", "vtx_rec");
+  p.vtx_coef = P<const double>(c, b, "scratch", "vtx_coef");
   p.zb_p = P<const double>(c, b, "scratch", "zb_p");
   p.zb_m = P<const double>(c, b, "scratch", "zb_m");
   MI(bdyMaskCell); MI(bdyMaskEdge); MI(nearestRelaxationCell);
@@ -935,6 +956,32 @@ int compute_bnd(mpas_dyc_ctx* ctx) {
                          P<double>(ctx, b, "scratch", "zb_m"));
       HIPCHK(hipGetLastError());
     }
+    {
+      int* bad = nullptr;
+      HIPCHK(hipMalloc(&bad, sizeof(int)));
+      HIPCHK(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+      hipLaunchKernelGGL(k_build_vtx_rec, dim3((d.nCells + 1 + 255) / 256), dim3(256), 0, ctx->stream, d,
+                         P<const int>(ctx, b, "mesh", "nEdgesOnCell"), P<const int>(ctx, b, "mesh", "edgesOnCell"),
+                         P<const int>(ctx, b, "mesh", "verticesOnCell"), P<const int>(ctx, b, "mesh", "edgesOnVertex"),
+                         P<const int>(ctx, b, "mesh", "cellsOnVertex"), P<const int>(ctx, b, "mesh", "kiteForCell"),
+                         P<const double>(ctx, b, "mesh", "edgesOnVertex_sign"), P<const double>(ctx, b, "mesh", "dcEdge"),
+                         P<const double>(ctx, b, "mesh", "dvEdge"), P<const double>(ctx, b, "mesh", "invAreaTriangle"),
+                         P<const double>(ctx, b, "mesh", "fVertex"), P<const double>(ctx, b, "mesh", "kiteAreasOnVertex"),
+                         P<int>(ctx, b, "scratch", "vtx_rec"),
+                         P<double>(ctx, b, "scratch", "vtx_coef"), bad);
+      if (d.nVertices > 0)
+        hipLaunchKernelGGL(k_check_vtx_writers, dim3((d.nVertices + 255) / 256), dim3(256), 0, ctx->stream, d,
+                           P<const int>(ctx, b, "mesh", "nEdgesOnCell"), P<const int>(ctx, b, "mesh", "verticesOnCell"),
+                           P<const int>(ctx, b, "mesh", "cellsOnVertex"), bad);
+      int h_bad = 1;
+      hipError_t e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      (void)hipFree(bad);
+      HIPCHK(e);
+      if (b.vtx_ok != (h_bad == 0)) drop_graphs(ctx);  // captured steps bake the choice of kernels in
+      b.vtx_ok = h_bad == 0;
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   ctx->bnd_ready = true;
@@ -1180,6 +1227,19 @@ bool recover_diag_fused(const mpas_dyc_ctx* ctx) {
   if (!ctx->fuse_recover_diag || needs_exchange(ctx) || ctx->lbc || ctx->blk.size() != 1) return false;
   if (ctx->cf.scalar_advection && !ctx->cf.split_dynamics_transport) return false;
   return pair_layout(ctx->blk[0].d);
+#endif
+}
+// Whether the diagnostics' cell kernel forms the vertex diagnostics of its own vertices
+// (diag_cells_vtx_col) and k_diag_vertices_p is not launched: one block whose cells are all owned,
+// without exchanges (the vertex kernel carries the u exchange's fused unpack), and a mesh on which
+// every vertex slot passed the record's checks; pair layout only.  Valid after compute_bnd.
+bool diag_vertices_fused(const mpas_dyc_ctx* ctx) {
+#ifdef MPAS_WIDE
+  return false;
+#else
+  if (!ctx->fuse_diag_vertices || needs_exchange(ctx) || ctx->blk.size() != 1) return false;
+  const Block& b = ctx->blk[0];
+  return pair_layout(b.d) && b.d.nCellsSolve == b.d.nCells && b.vtx_ok;
 #endif
 }
 // the sub-steps of each stage (atm_srk3, 296-322)
@@ -1488,6 +1548,23 @@ void solve_diagnostics(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, double d
     LAUNCH(k_diag_edges, d.nEdges, d, p, u, h, reconstruct_v, ctx->cf.apvm_upwinding, dt, store_grad);
     return;
   }
+#ifndef MPAS_WIDE
+  if (diag_vertices_fused(ctx)) {
+    // the cell kernel forms its vertices' values and stores pv_vertex (and vorticity): no vertex kernel
+    const double apvm = ctx->cf.apvm_upwinding;
+    if (rec3_hdiv >= 0) {
+      if (d.maxEdges == 6) LAUNCH((k_recover3_diag_cells_b<6, true>), d.nCells, d, p, rec3_hdiv, u, apvm, store_dv);
+      else LAUNCH((k_recover3_diag_cells_b<7, true>), d.nCells, d, p, rec3_hdiv, u, apvm, store_dv);
+    } else if (d.maxEdges == 6) {
+      LAUNCH(k_diag_cells_vtx_b<6>, d.nCells, d, p, u, apvm, store_dv);
+    } else {
+      LAUNCH(k_diag_cells_vtx_b<7>, d.nCells, d, p, u, apvm, store_dv);
+    }
+    if (d.maxEdges == 6) LAUNCH_PE((k_diag_edges_p<10, false>), (k_diag_edges_p<10, true>), d.nEdges, d, p, u, h, reconstruct_v, apvm, dt, store_grad);
+    else LAUNCH_PE((k_diag_edges_p<12, false>), (k_diag_edges_p<12, true>), d.nEdges, d, p, u, h, reconstruct_v, apvm, dt, store_grad);
+    return;
+  }
+#endif
   if (pair_layout(d)) {
     LAUNCH_PE((k_diag_vertices_p<false>), (k_diag_vertices_p<true>), d.nVertices, d, p, u, store_dv, uu_up,
               (tl == 1) ? p.u1 : p.u2);
@@ -2465,6 +2542,7 @@ int mpas_dyc_create_blocks(int32_t nblocks, const mpas_dyc_dims* dims, const mpa
   if (const char* ss = getenv("MPAS_DYCORE_SKIP_STAGE_AVG")) ctx->skip_stage_avg = std::string(ss) != "0";
   if (const char* fe = getenv("MPAS_DYCORE_FOLD_RK1_EDGES")) ctx->fold_rk1_edges = std::string(fe) != "0";
   if (const char* fr = getenv("MPAS_DYCORE_FUSE_RECOVER_DIAG")) ctx->fuse_recover_diag = std::string(fr) != "0";
+  if (const char* fv = getenv("MPAS_DYCORE_FUSE_DIAG_VERTICES")) ctx->fuse_diag_vertices = std::string(fv) != "0";
   if (const char* ov = getenv("MPAS_DYCORE_OVERLAP")) ctx->overlap = std::atoi(ov);
   for (auto& b : ctx->blk) {
     build_registry(b);
@@ -2568,7 +2646,8 @@ void* mpas_dyc_block_field_device_ptr(mpas_dyc_ctx* ctx, int32_t block, const ch
   if (!f) return nullptr;
   // the kernels read packed copies of the maxEdges-strided mesh fields (pack_mesh) and zb_cell / zb3_cell
   // through zb_p / zb_m: a caller may write through the pointer, so the next step packs them again
-  if (f->me || (f->pool == "mesh" && (f->name == "zb_cell" || f->name == "zb3_cell"))) ctx->bnd_ready = false;
+  if (f->me || rec_input(*f) || (f->pool == "mesh" && (f->name == "zb_cell" || f->name == "zb3_cell")))
+    ctx->bnd_ready = false;
   coefs_touched(ctx, *f);
   return f->buf[slot_of(ctx, *f, time_level)];
 }
@@ -2609,7 +2688,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
   if (!f->buf[slot])  // a G_ON_SET field alone, filled below; a hook's group whole: the others are zero until set
     CHK(f->group == G_ON_SET ? alloc_field(ctx, b, *f, false)
                              : alloc_group(ctx, f->group, GROUPS[f->group].all_blocks ? nullptr : &b));
-  if (f->me) ctx->bnd_ready = false;  // pack_mesh copies the new image for the kernels
+  if (f->me || rec_input(*f)) ctx->bnd_ready = false;  // pack_mesh copies the new image for the kernels
   coefs_touched(ctx, *f);
   if (f->is_int && f->target != T_NONE) {
     // MPAS 1-based -> device 0-based; out-of-range / 0 -> garbage slot
@@ -2665,6 +2744,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
       ctx->bnd_ready = false;
     }
     if (f->pool == "mesh" && (f->name == "zb_cell" || f->name == "zb3_cell")) ctx->bnd_ready = false;  // zb_p / zb_m
+    if (rec_input(*f)) ctx->bnd_ready = false;
     if (f->pool == "tend" && f->name == "rt_diabatic_tend") {
       const double* h = (const double*)host;
       int nz = 0;
@@ -2900,7 +2980,7 @@ int mpas_dyc_halo_exchange(mpas_dyc_ctx* ctx, const char* pool, const char* name
   HIPCHK(hipGetLastError());
   for (auto& b : ctx->blk) {
     const Field* f = find(b, pool, name);
-    if (f && f->me) ctx->bnd_ready = false;  // a maxEdges-strided mesh field: pack_mesh copies it again
+    if (f && (f->me || rec_input(*f))) ctx->bnd_ready = false;  // pack_mesh copies it again, the records its values
   }
   return MPAS_DYC_OK;
 }
@@ -3617,6 +3697,7 @@ int mpas_dyc_folded_passes(mpas_dyc_ctx* ctx) {
   bool drv = !ctx->blk.empty();
   for (const auto& b : ctx->blk) drv = drv && coefs_derived(ctx, b.d);
   if (drv) m |= 16;
+  if (diag_vertices_fused(ctx)) m |= 32;
   return m;
 }
 

@@ -392,6 +392,82 @@ __global__ void k_build_cell_rec(Dims d, const int* __restrict__ noc, const int*
   rec[(size_t)c * CELL_REC + 15] = bits;
 }
 
+// Per-cell vertex records (dycore.h, Ptrs::vtx_rec / vtx_coef), one thread per cell, and the checks
+// of what diag_cells_vtx_col relies on: vertex slot i of the cell touches the cell's edges i and
+// i-1 (mod nEdgesOnCell) and exactly one other edge, and the vertex's three cells are in the block.
+// The coefficients are the products k_diag_vertices_p forms.  *bad is set when an element fails; the
+// block then keeps k_diag_vertices_p (diag_vertices_fused).
+__global__ void k_build_vtx_rec(Dims d, const int* __restrict__ noc, const int* __restrict__ eoc,
+                                const int* __restrict__ voc, const int* __restrict__ eov,
+                                const int* __restrict__ cov, const int* __restrict__ kfc,
+                                const double* __restrict__ sign_v, const double* __restrict__ dcEdge,
+                                const double* __restrict__ dvEdge, const double* __restrict__ iat,
+                                const double* __restrict__ fVertex, const double* __restrict__ kites, int* rec,
+                                double* coef, int* bad) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c > d.nCells) return;
+  const int ME = d.maxEdges;
+  int ne = (c < d.nCells) ? noc[c] : 0;
+  bool fail = false;
+  if (c < d.nCells && (ne < 3 || ne > ME || ne > CELL_REC_ME)) fail = true, ne = 0;
+  int writers = 0;
+  for (int i = 0; i < CELL_REC_ME; ++i) {
+    int ev[3] = {d.nEdges, d.nEdges, d.nEdges};
+    double cf[VTX_COEF];
+    for (int m = 0; m < VTX_COEF; ++m) cf[m] = 0.0;
+    if (i < ne) {
+      const int v = voc[(size_t)c * ME + i];
+      const int eo = eoc[(size_t)c * ME + i], ep = eoc[(size_t)c * ME + (i + ne - 1) % ne];
+      if (v < 0 || v >= d.nVertices) {
+        fail = true;
+      } else {
+        int n[3] = {0, 0, 0};
+        for (int j = 0; j < 3; ++j) {
+          const int e = eov[3 * v + j], cc = cov[3 * v + j];
+          if (e < 0 || e >= d.nEdges || cc < 0 || cc >= d.nCells) {
+            fail = true;
+            continue;
+          }
+          ++n[e == eo ? 0 : (e == ep ? 1 : 2)];  // own edge i, own edge i-1, the spoke
+          ev[j] = e;
+          cf[j] = sign_v[3 * v + j] * dcEdge[e];
+          cf[3 + j] = dcEdge[e] * dvEdge[e];
+        }
+        if (n[0] != 1 || n[1] != 1 || n[2] != 1 || eo < 0 || eo >= d.nEdges) {
+          fail = true;
+        } else {
+          cf[6] = iat[v];
+          cf[7] = fVertex[v];
+          cf[8] = dcEdge[eo] * dvEdge[eo];
+          const int kj = kfc[(size_t)c * ME + i];
+          if (kj < 0 || kj > 2) fail = true;
+          else cf[9] = kites[3 * v + kj];
+          if (cov[3 * v] == c) writers |= 1 << i;
+        }
+      }
+    }
+    for (int j = 0; j < 3; ++j) rec[(size_t)c * VTX_REC + 3 * i + j] = ev[j];
+    if (i < ME)
+      for (int m = 0; m < VTX_COEF; ++m) coef[((size_t)c * ME + i) * VTX_COEF + m] = cf[m];
+  }
+  rec[(size_t)c * VTX_REC + 3 * CELL_REC_ME] = writers;
+  if (fail) *bad = 1;
+}
+// Every vertex has exactly one writer among the records: its cellsOnVertex(1) is a cell of the
+// block and holds the vertex in exactly one of its slots.  One thread per vertex.
+__global__ void k_check_vtx_writers(Dims d, const int* __restrict__ noc, const int* __restrict__ voc,
+                                    const int* __restrict__ cov, int* bad) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= d.nVertices) return;
+  const int c = cov[3 * v];
+  int n = 0;
+  if (c >= 0 && c < d.nCells) {
+    const int ne = min(noc[c], d.maxEdges);
+    for (int i = 0; i < ne; ++i) n += voc[(size_t)c * d.maxEdges + i] == v;
+  }
+  if (n != 1) *bad = 1;
+}
+
 // A cell's stencil from its record: one scalar round trip (see k_build_cell_rec).
 template <int ME>
 struct CellSten {
@@ -2459,6 +2535,33 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_dyn_advflux_p(Dims d, Ptrs p) 
   }
 }
 
+// ld_uniform_f64 for an array that no kernel writes while this one runs (a mesh field or a record),
+// read through the constant address space: the load is scalar wherever it stands, also after the
+// kernel's own stores, where the proof that nothing clobbered it may give up.
+typedef const __attribute__((address_space(4))) int* const_int_p;
+__device__ __forceinline__ int ld_const_i32(const int* a) { return *(const_int_p)a; }
+__device__ __forceinline__ double ld_const_f64(const double* a) {
+  const_int_p q = (const_int_p)a;
+  return __hiloint2double(q[1], q[0]);
+}
+
+// One level of a vertex's vorticity, ke_vertex and pv_vertex (5606-5622, 5665-5680) from u at its
+// three edges in edgesOnVertex order.  sd = edgesOnVertex_sign * dcEdge, ef = dcEdge * dvEdge.
+// k_diag_vertices_p and the cell kernels that form their vertices themselves (diag_cells_vtx_col)
+// both call this, so a vertex value has the same bits wherever it is formed.
+__device__ __forceinline__ void diag_vertex_vals(const double (&sd)[3], const double (&ef)[3], double u0, double u1,
+                                                 double u2, double iat, double fv, double& vort, double& kev,
+                                                 double& pv) {
+  double s = 0.0;
+  s = s + sd[0] * u0;
+  s = s + sd[1] * u1;
+  s = s + sd[2] * u2;
+  vort = s * iat;
+  const double r = 0.25 * iat;
+  kev = (ef[0] * (u0 * u0) + ef[1] * (u1 * u1) + ef[2] * (u2 * u2)) * r;
+  pv = fv + vort;
+}
+
 // k_diag_vertices in the pair layout: two vertices per wavefront, two levels per lane (16-byte
 // gathers of u at the three edges); same expressions in the same order
 // uu_up: the u exchange's fused unpack (988, XUnpack with write-back vertices): a received halo edge's u
@@ -2501,23 +2604,14 @@ __global__ __launch_bounds__(PAIR_THREADS) void k_diag_vertices_p(Dims d, Ptrs p
   }
   const double iat = sel(h, ld_uniform_f64(p.invAreaTriangle + vA), ld_uniform_f64(p.invAreaTriangle + vB));
   const double fv = sel(h, ld_uniform_f64(p.fVertex + vA), ld_uniform_f64(p.fVertex + vB));
-  d2 vort{0.0, 0.0};
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    vort.x = vort.x + sd[i] * uu[i].x;
-    vort.y = vort.y + sd[i] * uu[i].y;
-  }
-  vort.x = vort.x * iat;
-  vort.y = vort.y * iat;
-  const double r = 0.25 * iat;
-  d2 kev;
-  kev.x = (ef[0] * (uu[0].x * uu[0].x) + ef[1] * (uu[1].x * uu[1].x) + ef[2] * (uu[2].x * uu[2].x)) * r;
-  kev.y = (ef[0] * (uu[0].y * uu[0].y) + ef[1] * (uu[1].y * uu[1].y) + ef[2] * (uu[2].y * uu[2].y)) * r;
+  d2 vort, kev, pv;
+  diag_vertex_vals(sd, ef, uu[0].x, uu[1].x, uu[2].x, iat, fv, vort.x, kev.x, pv.x);
+  diag_vertex_vals(sd, ef, uu[0].y, uu[1].y, uu[2].y, iat, fv, vort.y, kev.y, pv.y);
   if ((h == 0 || hasB) && 2 * l < K) {
     const size_t o = (size_t)v * K + 2 * lc;
     if (store_dv) pst(p.vorticity + o, vort, two);
     pst(p.ke_vertex + o, kev, two);
-    pst(p.pv_vertex + o, d2{fv + vort.x, fv + vort.y}, two);
+    pst(p.pv_vertex + o, pv, two);
   }
 }
 
@@ -4360,6 +4454,94 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_diag_cells_b(Dims d, Ptrs p, 
   diag_cells_col<ME>(d, p, c, u, apvm, store_dv);
 }
 #ifndef MPAS_WIDE
+// diag_cells_col with the cell's vertices formed in registers instead of read from what
+// k_diag_vertices_p stored, which is then not launched (dycore.hip, diag_vertices_fused).  Vertex
+// slot i of a cell touches the cell's own edges i and i-1 (mod ne); its third edge (the spoke)
+// separates the two neighbouring cells (k_build_vtx_rec checks this on every slot).  So 12 columns
+// of u -- the 6 own edges this kernel loads anyway and the 6 spokes -- hold all that the six
+// vertices read: u is streamed once instead of twice, and ke_vertex is neither stored nor gathered.
+// The record names each vertex's three edges in edgesOnVertex order, and the three columns are
+// loaded in that order (two of the three are columns the wave loads anyway and hit in L1), all
+// before the first use.  Loading the 12 distinct columns once and placing them with wave-uniform
+// selects measured slower (72 64-bit selects per column).  diag_vertex_vals evaluates k_diag_vertices_p's expressions on the three values,
+// so kv and pv are the doubles that kernel stores.  Each vertex is formed by its three cells (the
+// same bits in each); the one that is its cellsOnVertex(1) stores pv_vertex (and vorticity).
+template <int ME>
+__device__ __forceinline__ void diag_cells_vtx_col(const Dims& d, const Ptrs& p, int c, const double* __restrict__ u,
+                                                   double apvm, int store_dv) {
+  const int k = lane_id(), K = d.K;
+  if (k >= K) return;
+  const int ne = p.nEdgesOnCell[c];
+  const int* vr = p.vtx_rec + (size_t)c * VTX_REC;
+  int ei[ME], vi[ME], ev[ME][3];
+#pragma unroll
+  for (int i = 0; i < ME; ++i) {
+    ei[i] = p.edgesOnCell[(size_t)c * ME + i];
+    vi[i] = p.verticesOnCell[(size_t)c * ME + i];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ev[i][j] = ld_const_i32(vr + 3 * i + j);
+  }
+  const int writers = ld_const_i32(vr + 3 * CELL_REC_ME);
+  const double r = ld_const_f64(p.invAreaCell + c);
+  double ue[ME], uv[ME][3];
+#pragma unroll
+  for (int i = 0; i < ME; ++i) ue[i] = u[(size_t)uni(ei[i]) * K + k];
+#pragma unroll
+  for (int i = 0; i < ME; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) uv[i][j] = u[(size_t)uni(ev[i][j]) * K + k];
+  }
+  // divergence (5626-5640) and the edge part of ke (5650-5660), as diag_cells_col: its sg * dv is
+  // cell_sdv, and its dc * dv is the record's product for the slot's own edge, the same doubles
+  double div = 0.0, ke = 0.0;
+#pragma unroll
+  for (int i = 0; i < ME; ++i) {
+    const double* vc = p.vtx_coef + ((size_t)c * ME + i) * VTX_COEF;
+    const double efo = ld_const_f64(vc + 8);
+    if (i < ne) {
+      div = div + ld_const_f64(p.cell_sdv + (size_t)c * ME + i) * ue[i];
+      ke = ke + 0.25 * (efo * (ue[i] * ue[i]));  // ke_edge (5600)
+    }
+  }
+  div = div * r;
+  ke = ke * r;
+  const double ke_fact = 1.0 - .375;
+  ke = ke_fact * ke;
+  double pvc = 0.0;
+#pragma unroll
+  for (int i = 0; i < ME; ++i) {
+    const double* vc = p.vtx_coef + ((size_t)c * ME + i) * VTX_COEF;
+    const double kite = ld_const_f64(vc + 9);
+    double sd[3], ef[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      sd[j] = ld_const_f64(vc + j);
+      ef[j] = ld_const_f64(vc + 3 + j);
+    }
+    double vort, kv, pv;
+    diag_vertex_vals(sd, ef, uv[i][0], uv[i][1], uv[i][2], ld_const_f64(vc + 6), ld_const_f64(vc + 7), vort, kv, pv);
+    if (i < ne) {
+      ke = ke + (1. - ke_fact) * kite * kv * r;
+      pvc = pvc + kite * (apvm > 0.0 ? pv : 0.0) * r;
+      if ((writers >> i) & 1) {
+        const size_t ov = (size_t)uni(vi[i]) * K + k;
+        if (store_dv) p.vorticity[ov] = vort;
+        p.pv_vertex[ov] = pv;
+      }
+    }
+  }
+  const size_t o = (size_t)c * K + k;
+  if (store_dv) p.divergence[o] = div;
+  p.ke[o] = ke;
+  if (apvm > 0.0) p.pv_cell[o] = pvc;
+}
+template <int ME>
+__global__ __launch_bounds__(BLOCK_THREADS) void k_diag_cells_vtx_b(Dims d, Ptrs p, const double* __restrict__ u,
+                                                                    double apvm, int store_dv) {
+  const int c = wave_elem(0);
+  if (c >= d.nCells) return;
+  diag_cells_vtx_col<ME>(d, p, c, u, apvm, store_dv);
+}
 // The w recovery (k_recover_cells3_b, phase 0) and the diagnostics' cell kernel (k_diag_cells_b) of
 // column c in one launch, after k_diag_vertices_p: srk3 runs them back to back when nothing lies
 // between them (one block without exchanges or LBCs, transport outside the dynamics), and
@@ -4367,14 +4549,16 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_diag_cells_b(Dims d, Ptrs p, 
 // only the cell's index row, so no stream is saved: both are latency-bound one-wavefront-per-column
 // kernels, and the launch saves one kernel's tail per call.  Same device functions
 // as the two kernels, so the bits are theirs.
-template <int ME>
+// VTX: the diagnostics half forms its vertices itself (diag_cells_vtx_col)
+template <int ME, bool VTX = false>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_recover3_diag_cells_b(Dims d, Ptrs p, int hdiv,
                                                                          const double* __restrict__ u, double apvm,
                                                                          int store_dv) {
   const int c = wave_elem(0);
   if (c >= d.nCells) return;
   recover_cells3_col<ME>(d, p, c, 0, hdiv);
-  diag_cells_col<ME>(d, p, c, u, apvm, store_dv);
+  if (VTX) diag_cells_vtx_col<ME>(d, p, c, u, apvm, store_dv);
+  else diag_cells_col<ME>(d, p, c, u, apvm, store_dv);
 }
 #endif
 

@@ -589,9 +589,12 @@ class Dycore:
         form cofwr, a_tri and gamma_tri in registers and only the dt's last coefficient call stores
         them: reported while the coefficient arrays are those of this context's last coefficient call,
         so not before the first step and not after a set of one of them
-        (MPAS_DYCORE_DERIVE_COEFS=0: off).  () when none applies."""
+        (MPAS_DYCORE_DERIVE_COEFS=0: off); "diag_vertices" -- the diagnostics' cell kernel forms its
+        vertices' vorticity, ke_vertex and pv_vertex itself, k_diag_vertices_p is not launched and
+        ke_vertex is not stored (one block, all cells owned, a mesh whose vertex slots follow the edge
+        slots; MPAS_DYCORE_FUSE_DIAG_VERTICES=0: off).  () when none applies."""
         m = int(self.lib.mpas_dyc_folded_passes(self.h))
-        names = ("substep_avg", "rk1_edges", "recover_diag", "stage_avg_stores", "derived_coefs")
+        names = ("substep_avg", "rk1_edges", "recover_diag", "stage_avg_stores", "derived_coefs", "diag_vertices")
         return tuple(n for i, n in enumerate(names) if m & (1 << i))
 
     def exchange_profile(self, dt: float, itimestep: int = 1) -> dict:

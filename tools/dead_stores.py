@@ -11,7 +11,8 @@ reads after the step.  Each candidate was checked by hand.
 The stores that a launch skips by its place in the dt, which its name does not show, are modelled
 (stage_drops): the recoveries of stages 1 and 2 store no ruAvg / wwAvg (SA_SKIP; --all-stage-stores
 for a trace taken with MPAS_DYCORE_SKIP_STAGE_AVG=0), and with the deriving cell phases in the trace
-only the dt's last k_vert_imp_coefs_p stores cofwr, a_tri and gamma_tri (store_drv).
+only the dt's last k_vert_imp_coefs_p stores cofwr, a_tri and gamma_tri (store_drv); the diagnostics'
+cell kernel stores divergence and vorticity only after stage 3 (store_dv).
 
     python tools/dead_stores.py gpurun_out/prof/run_kernel_trace.csv
 """
@@ -27,6 +28,7 @@ from kernel_access import access_map  # noqa: E402
 
 
 FIN_CELLS = re.compile(r"k_acoustic_cells_r<\d, true|k_dyn_cells3_acoustic_r<\d, (true|false), true")
+DIAG_CELLS = re.compile(r"k_recover3_diag_cells_b<|k_diag_cells_b<|k_diag_cells_vtx_b<")
 DRV_CELLS = re.compile(r"k_acoustic_cells_r<\d, (true|false), [1-7]>|k_dyn_cells3_acoustic_r<\d, (true|false), (true|false), [1-7]>")
 
 
@@ -42,6 +44,11 @@ def stage_drops(seq, ndt, skip_stage_avg=True):
             for j, i in enumerate([i for i, k in enumerate(seq) if pick(k)]):
                 if j % 3 != 2:
                     drops[i].add(member)
+    # the diagnostics' cell kernel stores divergence (and, where it forms the vertices, vorticity) only
+    # after stage 3 (store_dv): every third launch
+    for j, i in enumerate([i for i, k in enumerate(seq) if DIAG_CELLS.match(k)]):
+        if j % 3 != 2:
+            drops[i] |= {"divergence", "vorticity"}
     if any(DRV_CELLS.match(k) for k in seq):
         vic = [i for i, k in enumerate(seq) if k.startswith("k_vert_imp_coefs_p")]
         per = len(vic) // ndt

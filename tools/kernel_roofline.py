@@ -87,9 +87,17 @@ VARIANT = {
        for k, vs in (("k_acoustic_cells_r", ("false", "true")),
                      ("k_dyn_cells3_acoustic_r", ("true, true", "false, true", "false, false"))) for v in vs},
     "k_diag_edges_p": {"drop_w": {"gradPVn", "gradPVt"}},
+    # the diagnostics half forms its vertices from u and the vertex records (diag_cells_vtx_col): it
+    # gathers neither ke_vertex nor pv_vertex and takes dc * dv from the record; the other form reads
+    # no record and stores no vertex field
+    **{f"k_recover3_diag_cells_b<{me}, true": {"drop": {"ke_vertex", "pv_vertex", "dcEdge", "dvEdge", "kiteForCell",
+                                                        "kiteAreasOnVertex"}} for me in (6, 7)},
+    **{f"k_recover3_diag_cells_b<{me}{v}": {"drop": {"vtx_rec", "vtx_coef"}, "drop_w": {"pv_vertex", "vorticity"}}
+       for me in (6, 7) for v in (", false", ">")},  # "<6>": traces from before the second parameter
 }
 EXTRA_READS = {  # pointer arguments, not Ptrs members
     "k_diag_vertices": {"state.u"}, "k_diag_cells_b": {"state.u"}, "k_diag_vertices_p": {"state.u"},
+    "k_diag_cells_vtx_b": {"state.u"}, "k_recover3_diag_cells_b": {"state.u"},
     "k_diag_edges_p": {"state.u", "state.rho_zz"}, "k_reconstruct": {"state.u"}, "k_reconstruct_b": {"state.u"},
 }
 
@@ -119,7 +127,7 @@ def registry(nC, K, ME=6, ME2=10, ns=1):
     """pool.name -> (elements incl. the garbage slot, doubles per element), from build_registry."""
     nE, nV = 3 * nC - 6, 2 * nC - 4
     n = {"L_CELL": nC + 1, "L_EDGE": nE + 1, "L_VERTEX": nV + 1, "L_NONE": 1}
-    env = {"K": K, "ME": ME, "ME2": ME2, "ns": ns, "CELL_REC": 16}
+    env = {"K": K, "ME": ME, "ME2": ME2, "ns": ns, "CELL_REC": 16, "VTX_REC": 24, "VTX_COEF": 10}
     src = open(DYCORE).read()
     body = src[src.index("void build_registry"):src.index("Field* find(")]
     out = {}
@@ -189,7 +197,7 @@ def alg_bytes(kernel_full, amap, reg, ns=1):
 
 INT_FIELDS = {"nEdgesOnCell", "edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "cellsOnEdge",
               "verticesOnEdge", "nEdgesOnEdge", "edgesOnEdge", "nAdvCellsForEdge", "advCellsForEdge",
-              "cellsOnVertex", "edgesOnVertex", "cell_rec"}
+              "cellsOnVertex", "edgesOnVertex", "cell_rec", "vtx_rec"}
 
 
 def main():
