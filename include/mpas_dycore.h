@@ -283,6 +283,72 @@ int mpas_dyc_set_microphysics(mpas_dyc_ctx* ctx, int32_t scheme, int32_t index_q
  * with dt_microp = dt on time_level (1 or 2).  Asynchronous on the compute stream (synchronous only
  * while mpas_dyc_set_profile is on, which times it: mpas_dyc_get_profile out[7]). */
 int mpas_dyc_microphysics(mpas_dyc_ctx* ctx, double dt, int32_t time_level);
+/* The isobaric output diagnostics and mslp of the reference's `diagnostics` stream
+ * (diagnostics/isobaric_diagnostics.F, Registry_isobaric.xml), on the device (isobaric.hip), so a run
+ * that writes them need not copy ten 3-D fields to the host at output time.  One bit per group, because
+ * the reference computes a whole group when any member of it will be written (:96-259).  The fields are
+ * in the diag pool, Fortran images with the garbage slot:
+ *   <group>_{200,250,500,700,850,925}hPa for the first eight groups, each (nCells+1), vorticity_*hPa
+ *   (nVertices+1); mslp, meanT_500_300 (nCells+1); t_isobaric (5, nCells+1), z_isobaric (13, nCells+1);
+ *   t_iso_levels (5), z_iso_levels (13); and the one new input relhum (nVertLevels, nCells+1).
+ * They are allocated, zeroed, at the first mpas_dyc_set_field of one of them or at mpas_dyc_set_isobaric
+ * with a non-zero mask -- a context that asks for neither holds none of them (mpas_dyc_field_bytes
+ * returns 0) and behaves as before -- and set_field / get_field / field_bytes / field_device_ptr work
+ * on them from then on.  t_iso_levels (30000 .. 50000 Pa) and z_iso_levels (30000 .. 90000 Pa) are filled
+ * with the reference's constants (:479-501) when the group is allocated.  diag.relhum is an input: the
+ * reference's compute_relhum belongs to the physics' l_diags branch and stays with the host, which sets
+ * the field; it is 0.0 until set.
+ * mpas_dyc_set_isobaric(flags): the groups mpas_dyc_isobaric_diagnostics computes.  Unknown bits:
+ * MPAS_DYC_EINVAL.  On a MPAS_DYC_HOST_ONLY context the mask is kept and nothing is allocated. */
+#define MPAS_DYC_ISO_TEMPERATURE   1     /* temperature_{200,250,500,700,850,925}hPa      NEED_TEMP        */
+#define MPAS_DYC_ISO_RELHUM        2     /* relhum_*hPa                                   NEED_RELHUM      */
+#define MPAS_DYC_ISO_DEWPOINT      4     /* dewpoint_*hPa                                 NEED_DEWPOINT    */
+#define MPAS_DYC_ISO_UZONAL        8     /* uzonal_*hPa                                   NEED_UZONAL      */
+#define MPAS_DYC_ISO_UMERIDIONAL   16    /* umeridional_*hPa                              NEED_UMERIDIONAL */
+#define MPAS_DYC_ISO_HEIGHT        32    /* height_*hPa                                   NEED_HEIGHT      */
+#define MPAS_DYC_ISO_W             64    /* w_*hPa                                        NEED_W           */
+#define MPAS_DYC_ISO_VORTICITY     128   /* vorticity_*hPa (per vertex)                   NEED_VORTICITY   */
+#define MPAS_DYC_ISO_MSLP          256   /* mslp                                          need_mslp        */
+#define MPAS_DYC_ISO_T_ISOBARIC    512   /* t_isobaric (5, nCells+1), t_iso_levels        need_t_isobaric  */
+#define MPAS_DYC_ISO_Z_ISOBARIC    1024  /* z_isobaric (13, nCells+1), z_iso_levels       need_z_isobaric  */
+#define MPAS_DYC_ISO_MEANT_500_300 2048  /* meanT_500_300                                 need_meanT_500_300 */
+int mpas_dyc_set_isobaric(mpas_dyc_ctx* ctx, int32_t flags);
+/* interp_diagnostics(mesh, state, time_level, diag) (:265-895) of every block with the mask of
+ * mpas_dyc_set_isobaric, on the cells 1..nCellsSolve and the vertices 1..nVerticesSolve (halo elements
+ * and the garbage slot keep what they hold; the reference loops to nCells / nVertices, but its streams
+ * write owned elements only).  It reads w, theta_m and scalars(index_qv) of time_level (1 or 2; the
+ * reference passes 1, after the shift), diag.exner, pressure_p, pressure_base, relhum, and
+ * diag.vorticity and uReconstructZonal / Meridional as the last step left them, and mesh.zgrid;
+ * MPAS_DYC_ISO_VORTICITY also mesh.cellsOnVertex (the garbage cell's slot included), kiteAreasOnVertex
+ * and areaTriangle.  fp64 in the Fortran's operand order, no contraction:
+ *   pressure(k) = (pressure_p + pressure_base) / 100 (hPa); pressure2 at the K+1 interfaces (:517-542,
+ *   the top one through exp / log); pressure_v (:545-555); temperature and the Bolton dewpoint
+ *   (:561-569); interp_tofixed_pressure (:899-985) to 200 .. 925 hPa; t_isobaric / z_isobaric on
+ *   100 pressure / 100 pressure2 against levels in Pa; compute_layer_mean (:1139-1245);
+ *   mslp = 100 compute_slp (:988-1121).
+ * interp_tofixed_pressure couples the columns of a block only where some column's pressure is not
+ * strictly monotone; results are guaranteed for strictly monotone columns only, where the routine is
+ *   p(k+1) < p_out <= p(k) for some k:  (f(k+1) dpl + f(k) dpu) / (dpl + dpu), dpu = p_out - p(k+1),
+ *                                       dpl = p(k) - p_out;
+ *   else p_out < p(top): f(top) p_out / p(top);  else p_out > p(bottom): f(bottom);
+ *   else (p_out == p(top)): the bracket formula on the two topmost levels.
+ * compute_slp's failure paths (no level 100 hPa above the ground; klo == khi) set the whole block's
+ * mslp to 0.0, without a host synchronisation; the failure test runs over the owned cells only, not
+ * over 1..nCells as in the reference.
+ * Everything that does not pass through log / exp / pow has the reference's bits; dewpoint_*, mslp and
+ * whatever is interpolated in a bracket that contains the top interface's pressure2(K+1) pass through
+ * the device library's functions and agree with the C library's to the last bits.
+ * With MPAS_DYC_ISO_VORTICITY on a context that has exchange lists the call first exchanges the halo of
+ * diag.pressure_p, as mpas_dyc_halo_exchange(ctx, "diag", "pressure_p", 1, 7) does (:397-398): the vertex
+ * pressure of an owned vertex reads halo cells.  The call is therefore COLLECTIVE across ranks, like
+ * mpas_dyc_halo_exchange: every rank calls it, with the same mask.  No other bit needs a halo.
+ * Asynchronous on the compute stream (synchronous only while mpas_dyc_set_profile is on, which times
+ * its kernels: mpas_dyc_get_profile out[8]); always eager, never part of the step's captured graph,
+ * which stays as it is.  Mask 0: does nothing.  MPAS_DYC_EINVAL: time_level other than 1 or 2.
+ * MPAS_DYC_ESTATE: a MPAS_DYC_HOST_ONLY context; MPAS_DYC_ISO_VORTICITY without mesh.areaTriangle,
+ * kiteAreasOnVertex or cellsOnVertex set; between mpas_dyc_timestep and mpas_dyc_finish_step with
+ * MPAS_DYC_PHYSICS_MICROPHYSICS. */
+int mpas_dyc_isobaric_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level);
 /* Regional lateral boundary conditions, config_apply_lbcs (mpas_atm_time_integration.F:683-778,
  * 934-987, 1109-1180, 1253-1270, 1491-1560, 1672-1790; the routines at 6088-6671).  apply = 1 turns
  * them on (the pair kernel layout is required).  The host sets, as in the reference's lbc pool
@@ -545,7 +611,9 @@ double mpas_dyc_acoustic_bytes(const mpas_dyc_ctx* ctx);
  * stays put while steps replay (one capture per buffer layout and IAU branch, mpas_dyc_set_iau).
  * out[6] = ms of the last mpas_dyc_diag_update called with the profile on (HIP events around its
  * launches on the compute stream; that call is synchronous).
- * out[7] = the same for the last mpas_dyc_microphysics called with the profile on. */
+ * out[7] = the same for the last mpas_dyc_microphysics called with the profile on.
+ * out[8] = the same for the last mpas_dyc_isobaric_diagnostics called with the profile on (written
+ * only when n covers it, like every slot). */
 int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on);
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n);
 /* The plan key of the exchange whose RCCL group was enqueued last ("warm_rccl <key>" while the

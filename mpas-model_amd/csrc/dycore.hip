@@ -34,6 +34,7 @@
 #include "iau.hip"
 #include "convdiag.hip"
 #include "kessler.hip"
+#include "isobaric.hip"
 
 using namespace mpas;
 
@@ -46,7 +47,7 @@ enum Target { T_NONE, T_CELL, T_EDGE, T_VERTEX, T_SMALL };  // int index semanti
 // coefficients read (mpas_dyc_model_init, mpas_dyc_init_reconstruct).  The others belong to a step hook
 // (physics_host.hip) and are allocated together, zeroed, by alloc_group: when the hook is switched on,
 // or at the first set_field of one of them.
-enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP };
+enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP, G_ISOBARIC };
 // all_blocks: a first set_field completes the group on every block (false: on that block only).
 // hidden: mpas_dyc_block_field_bytes reports 0 until the field is allocated -- the fields are held
 // only by a context that asked for them.
@@ -56,6 +57,7 @@ constexpr struct { bool all_blocks, hidden; } GROUPS[] = {
     {false, false},  // G_IAU_SUMS: scratch.iau_*, the library's own; mpas_dyc_set_iau(on) allocates them
     {true, false},   // G_CONVDIAG: the convective running maxima
     {true, true},    // G_MICROP: the device microphysics' own fields
+    {true, true},    // G_ISOBARIC: the isobaric diagnostics' outputs, level tables and diag.relhum
 };
 
 struct Field {
@@ -108,6 +110,8 @@ struct Block {
   // cellsOnVertex (0-based), and the table the convective running maxima derive from it (convdiag_table)
   std::vector<int32_t> h_cov;
   ConvDiagTable cv;
+  bool kite_set = false;               // mesh.kiteAreasOnVertex has been set (the isobaric vorticity reads it)
+  int* iso_fail = nullptr;             // compute_slp's failure word of the block (isobaric.hip), on the device
   // maxEdges / maxEdges2 as the host declared them (the mesh file's dimensions; Fortran images and
   // h_eoc use these strides).  d.maxEdges / d.maxEdges2 are the strides the kernels index with:
   // max(nEdgesOnCell) and the edgesOnEdge slots the kernels need after pack_mesh
@@ -299,6 +303,7 @@ struct mpas_dyc_ctx {
   int summary_tl = 0;                   // time level the records describe (0: none yet)
   // the step hooks (physics_host.hip), each with its state struct next to its kernels
   IauState iau;                         // incremental analysis update (mpas_dyc_set_iau; iau.hip)
+  IsoState iso;                         // the isobaric diagnostics (mpas_dyc_set_isobaric; isobaric.hip)
   ConvDiagState convdiag;               // the convective running maxima (mpas_dyc_set_diag_update; convdiag.hip)
   MicropState microp;                   // the device microphysics (mpas_dyc_set_microphysics; kessler.hip)
   int64_t graph_captures = 0;           // steps captured so far (mpas_dyc_get_profile out[5])
@@ -359,6 +364,11 @@ int64_t field_bytes(const Block& b, const Field& f) { return field_elems(b, f) *
 
 bool is_host_0d(const Field& f) {
   return f.pool == "mesh" && (f.name == "cf1" || f.name == "cf2" || f.name == "cf3");
+}
+
+// <group>_<level>hPa of the isobaric diagnostics (isobaric.hip ISO_GROUPS, ISO_HPA)
+std::string iso_field_name(int group, int level) {
+  return std::string(ISO_GROUPS[group]) + "_" + std::to_string(ISO_HPA[level]) + "hPa";
 }
 
 // returns the new field: `add(...).group = G_...` for one that is not allocated with the context
@@ -547,6 +557,20 @@ void build_registry(Block& c) {
   add(c, "diag_physics", "i_rainnc", L_CELL, 1, 1, true).group = G_MICROP;
   add(c, "diag", "surface_pressure", L_CELL, 1).group = G_MICROP;
   add(c, "tend", "tend_sfc_pressure", L_CELL, 1).group = G_MICROP;
+  // the isobaric diagnostics (Registry_isobaric.xml, diag): the eight groups of six pressure levels
+  // (vorticity_*hPa per vertex), mslp, meanT_500_300, t_isobaric (5, nCells + 1), z_isobaric
+  // (13, nCells + 1), their level tables, and the host's relhum (K, nCells + 1), the one new input:
+  // allocated, zeroed, at the first set_field of one of them or at mpas_dyc_set_isobaric with a
+  // non-zero mask; the level tables then take the reference's constants (iso_init_field)
+  for (int g = 0; g < ISO_NGROUPS; ++g)
+    for (int l = 0; l < ISO_NP; ++l)
+      add(c, "diag", iso_field_name(g, l).c_str(), g == ISO_NGROUPS - 1 ? L_VERTEX : L_CELL, 1).group = G_ISOBARIC;
+  for (const char* n : {"mslp", "meanT_500_300"}) add(c, "diag", n, L_CELL, 1).group = G_ISOBARIC;
+  add(c, "diag", "t_isobaric", L_CELL, ISO_NT).group = G_ISOBARIC;
+  add(c, "diag", "z_isobaric", L_CELL, ISO_NZ).group = G_ISOBARIC;
+  add(c, "diag", "t_iso_levels", L_NONE, ISO_NT).group = G_ISOBARIC;
+  add(c, "diag", "z_iso_levels", L_NONE, ISO_NZ).group = G_ISOBARIC;
+  add(c, "diag", "relhum", L_CELL, K).group = G_ISOBARIC;
   // the maxEdges- and maxEdges2-strided mesh arrays (pack_mesh)
   for (const char* n : {"edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "coeffs_reconstruct",
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
@@ -743,13 +767,26 @@ int alloc_field(mpas_dyc_ctx* ctx, Block& b, Field& f, bool zero) {
   if (zero) HIPCHK(hipMemsetAsync(f.buf[0], 0, nb, ctx->stream));  // ordered before the stream's own work on it
   return MPAS_DYC_OK;
 }
+// t_iso_levels / z_iso_levels of the isobaric diagnostics take the reference's constants
+// (isobaric_diagnostics.F:479-501) when they are allocated, after the zeroing on the same stream
+int iso_init_field(mpas_dyc_ctx* ctx, Field& f) {
+  static const double t_lev[ISO_NT] = {30000.0, 35000.0, 40000.0, 45000.0, 50000.0};
+  static const double z_lev[ISO_NZ] = {30000.0, 35000.0, 40000.0, 45000.0, 50000.0, 55000.0, 60000.0,
+                                       65000.0, 70000.0, 75000.0, 80000.0, 85000.0, 90000.0};
+  if (f.name == "t_iso_levels") HIPCHK(hipMemcpyAsync(f.buf[0], t_lev, sizeof t_lev, hipMemcpyHostToDevice, ctx->stream));
+  if (f.name == "z_iso_levels") HIPCHK(hipMemcpyAsync(f.buf[0], z_lev, sizeof z_lev, hipMemcpyHostToDevice, ctx->stream));
+  return MPAS_DYC_OK;
+}
 // Every field of a group that has no buffer yet, on every block or on `only`, zeroed.  A call that
 // fails half-way leaves the rest unallocated (group_ready stays false), and the next one completes it.
 int alloc_group(mpas_dyc_ctx* ctx, Group g, Block* only = nullptr) {
   for (auto& b : ctx->blk) {
     if (only && &b != only) continue;
     for (auto& f : b.fields)
-      if (f.group == g && !f.buf[0]) CHK(alloc_field(ctx, b, f, true));
+      if (f.group == g && !f.buf[0]) {
+        CHK(alloc_field(ctx, b, f, true));
+        if (g == G_ISOBARIC) CHK(iso_init_field(ctx, f));
+      }
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));  // zeroed before a set_field / get_field of the caller
   return MPAS_DYC_OK;
@@ -2605,6 +2642,7 @@ void mpas_dyc_destroy(mpas_dyc_ctx* ctx) {
     if (b.sum_out) (void)hipFree(b.sum_out);
     if (b.cv.start) (void)hipFree(b.cv.start);
     if (b.cv.kite) (void)hipFree(b.cv.kite);
+    if (b.iso_fail) (void)hipFree(b.iso_fail);
   }
   if (ctx->sum_gather) (void)hipFree(ctx->sum_gather);
   p2p_teardown(ctx);  // after the plans (invalidate_plans above) and the field buffers: see there
@@ -2649,6 +2687,7 @@ void* mpas_dyc_block_field_device_ptr(mpas_dyc_ctx* ctx, int32_t block, const ch
   if (f->me || rec_input(*f) || (f->pool == "mesh" && (f->name == "zb_cell" || f->name == "zb3_cell")))
     ctx->bnd_ready = false;
   coefs_touched(ctx, *f);
+  if (f->pool == "mesh" && f->name == "kiteAreasOnVertex") b->kite_set = true;  // a caller may write through it
   return f->buf[slot_of(ctx, *f, time_level)];
 }
 
@@ -2745,6 +2784,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
     }
     if (f->pool == "mesh" && (f->name == "zb_cell" || f->name == "zb3_cell")) ctx->bnd_ready = false;  // zb_p / zb_m
     if (rec_input(*f)) ctx->bnd_ready = false;
+    if (f->pool == "mesh" && f->name == "kiteAreasOnVertex") b.kite_set = true;
     if (f->pool == "tend" && f->name == "rt_diabatic_tend") {
       const double* h = (const double*)host;
       int nz = 0;
@@ -3539,7 +3579,7 @@ int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on) {
 
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n) {
   if (!ctx || !out || n < 1) return MPAS_DYC_EINVAL;
-  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : 0.0;
+  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : i == 8 ? ctx->iso.ms : 0.0;
   return MPAS_DYC_OK;
 }
 

@@ -16,6 +16,10 @@ void hl_pow_v(const double* x, const double* y, double* out, int64_t n) {
 void hl_exp(const double* x, double* out, int64_t n) {
   for (int64_t i = 0; i < n; ++i) out[i] = exp(x[i]);
 }
+/* log: the isobaric diagnostics' dewpoint, top-interface pressure and compute_slp (mpas_dycore/isobaric.py) */
+void hl_log(const double* x, double* out, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) out[i] = log(x[i]);
+}
 void hl_asin(const double* x, double* out, int64_t n) {
   for (int64_t i = 0; i < n; ++i) out[i] = asin(x[i]);
 }

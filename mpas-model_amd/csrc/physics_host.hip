@@ -1,12 +1,13 @@
 // Host side of the step's physics hooks: the incremental analysis update (kernels: iau.hip), the
-// convective running maxima (convdiag.hip) and the device microphysics (kessler.hip).  Per hook: what
+// convective running maxima (convdiag.hip), the device microphysics (kessler.hip) and the isobaric output
+// diagnostics (isobaric.hip; not part of the step, but a hook of the same shape).  Per hook: what
 // enqueues its kernels, and its entry points of include/mpas_dycore.h.  A hook's state struct
 // (mpas_dyc_ctx::iau / convdiag / microp, Block::cv) stands next to its kernels' argument struct; its
 // fields are a Group of the registry (dycore.hip build_registry), allocated by alloc_group.
 //
 // Included by dycore.hip inside its namespace, before srk3: after the structs (Field, Block,
 // mpas_dyc_ctx), HIPCHK / CHK, find, P, field_bytes, physics_tendencies, drop_graphs, require_device,
-// alloc_group, group_ready, timed_on_stream and compute_bnd.  The file closes that namespace for its
+// alloc_group, group_ready, timed_on_stream, iso_field_name and compute_bnd.  The file closes that namespace for its
 // extern "C" entry points and opens it again at its end.
 
 // ---- incremental analysis update ----
@@ -156,9 +157,111 @@ int kessler_enqueue(mpas_dyc_ctx* ctx, double dt, int tl) {
   return MPAS_DYC_OK;
 }
 
+// ---- isobaric diagnostics ----
+// interp_diagnostics with the context's mask on time level tl of every block: the failure word's reset,
+// the cell kernel and mslp's failure pass, then the vertex kernel
+int iso_enqueue(mpas_dyc_ctx* ctx, int tl) {
+  const int flags = ctx->iso.flags;
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    const int K = d.K;
+    if ((flags & ~ISO_VORTICITY) && d.nCellsSolve > 0) {
+      IsoCells a{};
+      a.nCellsSolve = d.nCellsSolve, a.K = K, a.flags = flags;
+      a.pressure_p = P<const double>(ctx, b, "diag", "pressure_p");
+      a.pressure_base = P<const double>(ctx, b, "diag", "pressure_base");
+      a.theta_m = P<const double>(ctx, b, "state", "theta_m", tl);
+      a.qv = P<const double>(ctx, b, "state", "scalars", tl) + (int64_t)ctx->index_qv * (d.nCells + 1) * K;
+      a.exner = P<const double>(ctx, b, "diag", "exner");
+      a.relhum = P<const double>(ctx, b, "diag", "relhum");
+      a.uzonal = P<const double>(ctx, b, "diag", "uReconstructZonal");
+      a.umeridional = P<const double>(ctx, b, "diag", "uReconstructMeridional");
+      a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
+      a.w = P<const double>(ctx, b, "state", "w", tl);
+      for (int l = 0; l < ISO_NP; ++l) a.hpa[l] = (double)ISO_HPA[l];
+      for (int l = 0; l < ISO_NT; ++l) a.t_lev[l] = 30000.0 + 5000.0 * l;  // :479-501
+      for (int l = 0; l < ISO_NZ; ++l) a.z_lev[l] = 30000.0 + 5000.0 * l;
+      for (int g = 0; g < ISO_NGROUPS - 1; ++g)
+        for (int l = 0; l < ISO_NP; ++l) a.out[g][l] = P<double>(ctx, b, "diag", iso_field_name(g, l).c_str());
+      a.mslp = P<double>(ctx, b, "diag", "mslp");
+      a.t_isobaric = P<double>(ctx, b, "diag", "t_isobaric");
+      a.z_isobaric = P<double>(ctx, b, "diag", "z_isobaric");
+      a.meanT_500_300 = P<double>(ctx, b, "diag", "meanT_500_300");
+      if (flags & ISO_MSLP) {
+        if (!b.iso_fail) HIPCHK(hipMalloc(&b.iso_fail, 256));
+        HIPCHK(hipMemsetAsync(b.iso_fail, 0, 4, ctx->stream));
+      }
+      a.fail = b.iso_fail;
+      hipLaunchKernelGGL(k_iso_cells, dim3((unsigned)((d.nCellsSolve + ISO_WAVES - 1) / ISO_WAVES)), dim3(ISO_THREADS), 0,
+                         ctx->stream, a);
+      if (flags & ISO_MSLP)
+        hipLaunchKernelGGL(k_iso_mslp_fail, dim3((unsigned)((d.nCellsSolve + 255) / 256)), dim3(256), 0, ctx->stream,
+                           d.nCellsSolve, (const int*)b.iso_fail, a.mslp);
+    }
+    if ((flags & ISO_VORTICITY) && d.nVerticesSolve > 0) {
+      IsoVerts a{};
+      a.nVerticesSolve = d.nVerticesSolve, a.K = K;
+      a.pressure_p = P<const double>(ctx, b, "diag", "pressure_p");
+      a.pressure_base = P<const double>(ctx, b, "diag", "pressure_base");
+      a.vorticity = P<const double>(ctx, b, "diag", "vorticity");
+      a.kiteAreasOnVertex = P<const double>(ctx, b, "mesh", "kiteAreasOnVertex");
+      a.areaTriangle = P<const double>(ctx, b, "mesh", "areaTriangle");
+      a.cellsOnVertex = P<const int>(ctx, b, "mesh", "cellsOnVertex");
+      for (int l = 0; l < ISO_NP; ++l) {
+        a.hpa[l] = (double)ISO_HPA[l];
+        a.out[l] = P<double>(ctx, b, "diag", iso_field_name(ISO_NGROUPS - 1, l).c_str());
+      }
+      hipLaunchKernelGGL(k_iso_vertices, dim3((unsigned)((d.nVerticesSolve + ISO_WAVES - 1) / ISO_WAVES)), dim3(ISO_THREADS), 0,
+                         ctx->stream, a);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  return MPAS_DYC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mpas_dyc_set_isobaric(mpas_dyc_ctx* ctx, int32_t flags) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (flags & ~ISO_ALL) {
+    ctx->err = "mpas_dyc_set_isobaric: unknown flag bits";
+    return MPAS_DYC_EINVAL;
+  }
+  ctx->iso.flags = flags;
+  if (ctx->host_only || !flags) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!group_ready(ctx, G_ISOBARIC)) CHK(alloc_group(ctx, G_ISOBARIC));
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_isobaric_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level) {
+  if (!ctx || (time_level != 1 && time_level != 2)) return MPAS_DYC_EINVAL;
+  CHK(require_device(ctx));
+  if (ctx->tail_pending) {
+    ctx->err = "mpas_dyc_isobaric_diagnostics between mpas_dyc_timestep and mpas_dyc_finish_step";
+    return MPAS_DYC_ESTATE;
+  }
+  const int flags = ctx->iso.flags;
+  if (!flags) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!group_ready(ctx, G_ISOBARIC)) CHK(alloc_group(ctx, G_ISOBARIC));
+  if (flags & ISO_VORTICITY) {
+    bool lists = false;
+    for (auto& b : ctx->blk) {
+      if (!find(b, "mesh", "areaTriangle")->buf[0] || !b.kite_set || (int64_t)b.h_cov.size() < 3LL * b.d.nVertices) {
+        ctx->err = "mpas_dyc_isobaric_diagnostics: MPAS_DYC_ISO_VORTICITY needs mesh.areaTriangle, kiteAreasOnVertex and "
+                   "cellsOnVertex set";
+        return MPAS_DYC_ESTATE;
+      }
+      lists = lists || !b.xl.empty();
+    }
+    // the vertex pressure of an owned vertex reads halo cells (isobaric_diagnostics.F:397-398)
+    if (lists) CHK(mpas_dyc_halo_exchange(ctx, "diag", "pressure_p", 1, 7));
+  }
+  return timed_on_stream(ctx, ctx->iso.ms, [&]() -> int { return iso_enqueue(ctx, time_level); });
+}
 
 int mpas_dyc_set_physics(mpas_dyc_ctx* ctx, int32_t flags) {
   if (!ctx || (flags & ~(MPAS_DYC_PHYSICS_TENDENCIES | MPAS_DYC_PHYSICS_RQVDYNTEN | MPAS_DYC_PHYSICS_MICROPHYSICS)))

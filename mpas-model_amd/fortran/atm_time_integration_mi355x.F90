@@ -255,6 +255,16 @@ module atm_time_integration
          type(c_ptr), value :: ctx
          integer(c_int32_t), value :: flags
       end function
+      integer(c_int) function mpas_dyc_set_isobaric(ctx, flags) bind(C, name='mpas_dyc_set_isobaric')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: flags
+      end function
+      integer(c_int) function mpas_dyc_isobaric_diagnostics(ctx, time_level) bind(C, name='mpas_dyc_isobaric_diagnostics')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: time_level
+      end function
       integer(c_int) function mpas_dyc_set_summary(ctx, flags) bind(C, name='mpas_dyc_set_summary')
          import :: c_int, c_ptr, c_int32_t
          type(c_ptr), value :: ctx
@@ -316,6 +326,14 @@ module atm_time_integration
    logical, save, private :: diag_host_current = .false.
    character(len=32), dimension(3), parameter, private :: diag_max_names = [character(len=32) :: &
       'w_velocity_max', 'wind_speed_level1_max', 'updraft_helicity_max']   ! bit i-1 of the mask
+   ! the isobaric diagnostics (atm_dycore_isobaric_diagnostics): the groups of six pressure levels in the
+   ! bit order of the MPAS_DYC_ISO_* mask, their levels, and the single fields of bits 8 .. 11
+   character(len=32), dimension(8), parameter, private :: iso_groups = [character(len=32) :: &
+      'temperature', 'relhum', 'dewpoint', 'uzonal', 'umeridional', 'height', 'w', 'vorticity']
+   character(len=8), dimension(6), parameter, private :: iso_levels = [character(len=8) :: &
+      '200hPa', '250hPa', '500hPa', '700hPa', '850hPa', '925hPa']
+   character(len=32), dimension(4), parameter, private :: iso_single = [character(len=32) :: &
+      'mslp', 't_isobaric', 'z_isobaric', 'meanT_500_300']
    ! atm_dycore_plan_exchanges: the domain context as host-only contexts (no GPU, no uploads)
    logical, save, private :: plan_only = .false.
    integer(c_int64_t), save, private :: plan_id_sum = 0
@@ -553,6 +571,54 @@ module atm_time_integration
       end if
       call check(dyc, mpas_dyc_diag_reset(dyc, int(mask, c_int32_t)), 'mpas_dyc_diag_reset')
    end subroutine atm_dycore_diag_reset
+
+   ! interp_diagnostics (diagnostics/isobaric_diagnostics.F:265-895) on the device: what a host's
+   ! diagnostics_compute calls in place of interp_diagnostics(mesh, state, 1, diag), after the time levels
+   ! were shifted.  flags: the MPAS_DYC_ISO_* mask of the groups the streams are about to write (the
+   ! reference's NEED_* switches, one bit per group).  It uploads the host's diag relhum (compute_relhum
+   ! belongs to the physics and stays with the host) and, for the vorticity group, areaTriangle; runs
+   ! mpas_dyc_isobaric_diagnostics on time level 1; and downloads the enabled 2-D fields and the level
+   ! tables into the diag pool.  The 3-D state stays on the device.  With the vorticity group the call
+   ! exchanges the halo of pressure_p: every task calls it, with the same mask.
+   subroutine atm_dycore_isobaric_diagnostics(domain, flags)
+      type (domain_type), intent(inout) :: domain
+      integer, intent(in) :: flags
+      type (block_type), pointer :: block
+      type (mpas_pool_type), pointer :: mesh, diag
+      integer :: ib, g, l
+
+      if (.not. c_associated(dyc) .or. flags == 0) return
+      call check(dyc, mpas_dyc_set_isobaric(dyc, int(flags, c_int32_t)), 'mpas_dyc_set_isobaric')
+      block => domain % blocklist
+      ib = 0
+      do while (associated(block))
+         call mpas_pool_get_subpool(block % structs, 'mesh', mesh)
+         call mpas_pool_get_subpool(block % structs, 'diag', diag)
+         if (iand(flags, 2) /= 0) call xfer(dyc, ib, diag, 'diag', 'relhum', 1, 1, UP, .true.)
+         if (iand(flags, 128) /= 0) call xfer(dyc, ib, mesh, 'mesh', 'areaTriangle', 1, 1, UP, .true.)
+         ib = ib + 1
+         block => block % next
+      end do
+      call check(dyc, mpas_dyc_isobaric_diagnostics(dyc, 1_c_int32_t), 'mpas_dyc_isobaric_diagnostics')
+      block => domain % blocklist
+      ib = 0
+      do while (associated(block))
+         call mpas_pool_get_subpool(block % structs, 'diag', diag)
+         do g = 1, size(iso_groups)
+            if (iand(flags, ishft(1, g - 1)) == 0) cycle
+            do l = 1, size(iso_levels)
+               call xfer(dyc, ib, diag, 'diag', trim(iso_groups(g))//'_'//trim(iso_levels(l)), 1, 1, DOWN, .false.)
+            end do
+         end do
+         do g = 1, size(iso_single)
+            if (iand(flags, ishft(256, g - 1)) /= 0) call xfer(dyc, ib, diag, 'diag', trim(iso_single(g)), 1, 1, DOWN, .false.)
+         end do
+         if (iand(flags, 512) /= 0) call xfer(dyc, ib, diag, 'diag', 't_iso_levels', 1, 1, DOWN, .false.)
+         if (iand(flags, 1024) /= 0) call xfer(dyc, ib, diag, 'diag', 'z_iso_levels', 1, 1, DOWN, .false.)
+         ib = ib + 1
+         block => block % next
+      end do
+   end subroutine atm_dycore_isobaric_diagnostics
 
    ! Copy the device state into the host pools' time level 1 (the current one once the caller
    ! has shifted time levels after the step): prognostics, diagnostics, rthdynten / rqvdynten.

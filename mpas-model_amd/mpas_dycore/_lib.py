@@ -30,7 +30,7 @@ EXPORTS = (
     "mpas_dyc_init_deriv_two", "mpas_dyc_init_zb", "mpas_dyc_init_reconstruct", "mpas_dyc_comm_check",
     "mpas_dyc_fused_tend_acoustic", "mpas_dyc_set_iau", "mpas_dyc_iau_weight", "mpas_dyc_set_diag_update",
     "mpas_dyc_diag_update", "mpas_dyc_diag_reset", "mpas_dyc_folded_passes", "mpas_dyc_set_microphysics",
-    "mpas_dyc_microphysics",
+    "mpas_dyc_microphysics", "mpas_dyc_set_isobaric", "mpas_dyc_isobaric_diagnostics",
 )
 HOST_ONLY = -2  # MPAS_DYC_HOST_ONLY: planner-only context
 PRINT_GLOBAL_MINMAX_VEL, PRINT_DETAILED_MINMAX_VEL, PRINT_GLOBAL_MINMAX_SCA = 1, 2, 4
@@ -38,6 +38,10 @@ PRINT_GLOBAL_MINMAX_VEL, PRINT_DETAILED_MINMAX_VEL, PRINT_GLOBAL_MINMAX_SCA = 1,
 DIAG_W_VELOCITY_MAX, DIAG_WIND_SPEED_LEVEL1_MAX, DIAG_UPDRAFT_HELICITY_MAX = 1, 2, 4
 # MPAS_DYC_MICROP_*: the scheme of mpas_dyc_set_microphysics
 MICROP_OFF, MICROP_KESSLER = 0, 1
+# MPAS_DYC_ISO_*: the groups of mpas_dyc_isobaric_diagnostics
+(ISO_TEMPERATURE, ISO_RELHUM, ISO_DEWPOINT, ISO_UZONAL, ISO_UMERIDIONAL, ISO_HEIGHT, ISO_W, ISO_VORTICITY, ISO_MSLP,
+ ISO_T_ISOBARIC, ISO_Z_ISOBARIC, ISO_MEANT_500_300) = (1 << i for i in range(12))
+ISO_ALL = 4095
 CELL, EDGE, VERTEX = 0, 1, 2
 SEND, RECV = 0, 1
 
@@ -140,6 +144,8 @@ def load() -> C.CDLL:
     lib.mpas_dyc_diag_reset.argtypes = [vp, i32]
     lib.mpas_dyc_set_microphysics.argtypes = [vp, i32, i32, i32, dbl]
     lib.mpas_dyc_microphysics.argtypes = [vp, dbl, i32]
+    lib.mpas_dyc_set_isobaric.argtypes = [vp, i32]
+    lib.mpas_dyc_isobaric_diagnostics.argtypes = [vp, i32]
     lib.mpas_dyc_time_acoustic_step.argtypes = [vp, dbl, i32, i32, C.POINTER(dbl), C.POINTER(dbl)]
     lib.mpas_dyc_use_graph.argtypes = [vp, i32]
     lib.mpas_dyc_acoustic_bytes.argtypes = [vp]

@@ -37,7 +37,8 @@ _SKIP = set(STATE_INPUTS) | set(DIAG_INPUTS) | {"xCell", "yCell", "zCell", "xEdg
                                                 "latVertex", "lonVertex", "areaCell", "areaTriangle",
                                                 "meshDensity", "indexToCellID", "deriv_two", "zb", "zb3",
                                                 "w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max",
-                                                *F.MICROP_FIELD}
+                                                *F.MICROP_FIELD, *F.ISO_CELL_FIELDS, *F.ISO_VERTEX_FIELDS,
+                                                *F.ISO_LEVEL_TABLES}
 
 
 def _host_allgather_fn(group, nranks: int):
@@ -480,6 +481,55 @@ class Dycore:
         out = (C.c_double * 8)()
         self._check(self.lib.mpas_dyc_get_profile(self.h, out, 8), "get_profile")
         return float(out[7])
+
+    def set_isobaric(self, flags: int | None = None, **groups: bool):
+        """Which isobaric diagnostics isobaric_diagnostics() computes (mpas_dyc_set_isobaric; the
+        reference's NEED_* switches, isobaric_diagnostics.F:96-259).  ``flags``: the MPAS_DYC_ISO_* mask
+        (default: all), or keyword switches named like the constants of ``_lib`` without the prefix, e.g.
+        ``set_isobaric(temperature=True, mslp=True)``.  A non-zero mask allocates, zeroed, the diag
+        fields ``<group>_{200,250,500,700,850,925}hPa`` (vorticity_*hPa per vertex), ``mslp``,
+        ``meanT_500_300``, ``t_isobaric`` (5 per cell), ``z_isobaric`` (13 per cell), the level tables
+        ``t_iso_levels`` / ``z_iso_levels`` with the reference's constants, and the input ``relhum``
+        (K per cell; the host's compute_relhum sets it, 0.0 until then).  The vorticity group divides by
+        areaTriangle, which the step itself never reads: it is uploaded here from the case."""
+        if groups:
+            if flags is not None:
+                raise ValueError("set_isobaric: either flags or keyword switches")
+            flags = 0
+            for name, on in groups.items():
+                bit = getattr(_lib, "ISO_" + name.upper(), None)
+                if bit is None or name.upper() == "ALL":
+                    raise ValueError(f"set_isobaric: unknown group {name!r}")
+                flags |= bit if on else 0
+        elif flags is None:
+            flags = _lib.ISO_ALL
+        self._check(self.lib.mpas_dyc_set_isobaric(self.h, int(flags)), "set_isobaric")
+        if flags & _lib.ISO_VORTICITY:
+            for ib, c in enumerate(self.cases):
+                if "areaTriangle" in c:
+                    self.set_raw("mesh", "areaTriangle", to_fortran(c, "areaTriangle"), block=ib)
+
+    def isobaric_diagnostics(self, time_level: int = 1):
+        """interp_diagnostics (isobaric_diagnostics.F:265-895) on the owned cells and vertices of every
+        block with the mask of set_isobaric (mpas_dyc_isobaric_diagnostics), from w, theta_m and qv of
+        ``time_level``, diag.exner / pressure_p / pressure_base / relhum and the vorticity and
+        reconstructed winds the last step left: call it after shift_time_levels().  Asynchronous; never
+        part of the step's captured graph.  With the vorticity group on blocks that have exchange lists it
+        first exchanges the halo of diag.pressure_p: collective across ranks.  mpas_dycore.isobaric is
+        its numpy restatement."""
+        self._check(self.lib.mpas_dyc_isobaric_diagnostics(self.h, int(time_level)), "isobaric_diagnostics")
+
+    def isobaric_diagnostics_ms(self, time_level: int = 1) -> float:
+        """Milliseconds of one isobaric_diagnostics() call between HIP events (mpas_dyc_get_profile
+        out[8]); synchronous."""
+        self._check(self.lib.mpas_dyc_set_profile(self.h, 1), "set_profile")
+        try:
+            self.isobaric_diagnostics(time_level)
+        finally:
+            self._check(self.lib.mpas_dyc_set_profile(self.h, 0), "set_profile")
+        out = (C.c_double * 9)()
+        self._check(self.lib.mpas_dyc_get_profile(self.h, out, 9), "get_profile")
+        return float(out[8])
 
     def finish_step(self, dt: float):
         """The end of atm_srk3 after the host's microphysics (1672-1794); a no-op unless

@@ -50,6 +50,18 @@ MICROP_FIELD = {"rainnc": "diag_physics", "rainncv": "diag_physics", "precipw": 
 LOCATION.update({n: "cell" for n in MICROP_FIELD})
 INT_FIELDS = {"i_rainnc"}   # int32 on the device, not an index into an element set
 
+# the isobaric diagnostics (mpas_dyc_set_isobaric; diag pool): <group>_<level>hPa per cell, vorticity_*hPa
+# per vertex, mslp, meanT_500_300, t_isobaric (5 per cell), z_isobaric (13 per cell), the host's relhum (K per
+# cell); t_iso_levels (5) and z_iso_levels (13) have no horizontal location
+ISO_GROUPS = ("temperature", "relhum", "dewpoint", "uzonal", "umeridional", "height", "w", "vorticity")
+ISO_HPA = (200, 250, 500, 700, 850, 925)
+ISO_CELL_FIELDS = tuple(f"{g}_{p}hPa" for g in ISO_GROUPS[:-1] for p in ISO_HPA) + (
+    "mslp", "meanT_500_300", "t_isobaric", "z_isobaric", "relhum")
+ISO_VERTEX_FIELDS = tuple(f"vorticity_{p}hPa" for p in ISO_HPA)
+ISO_LEVEL_TABLES = ("t_iso_levels", "z_iso_levels")
+LOCATION.update({n: "cell" for n in ISO_CELL_FIELDS})
+LOCATION.update({n: "vertex" for n in ISO_VERTEX_FIELDS})
+
 VERTICAL_1D = ("fzm", "fzp", "rdzw", "rdzu", "u_init", "v_init")
 SCALARS_0D = ("cf1", "cf2", "cf3")
 
