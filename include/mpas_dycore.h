@@ -349,6 +349,54 @@ int mpas_dyc_set_isobaric(mpas_dyc_ctx* ctx, int32_t flags);
  * kiteAreasOnVertex or cellsOnVertex set; between mpas_dyc_timestep and mpas_dyc_finish_step with
  * MPAS_DYC_PHYSICS_MICROPHYSICS. */
 int mpas_dyc_isobaric_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level);
+/* The Ertel PV and dynamic-tropopause diagnostics of the reference's PV stream
+ * (diagnostics/pv_diagnostics.F, Registry_pv.xml), on the device (pv.hip), so a run that writes them need
+ * not copy w, theta_m, rho_zz, qv, uReconstructX/Y/Z and vorticity to the host at output time.  The
+ * fields, Fortran images with the garbage slot:
+ *   outputs, diag pool: ertel_pv (nVertLevels, nCells+1) in PVU; iLev_DT (int32, nCells+1), the level
+ *     above the dynamic tropopause (0: the whole column is above 2 PVU, nVertLevels+1: below); u_pv, v_pv,
+ *     theta_pv, vort_pv (nCells+1), the zonal and meridional wind, theta and the cell's vertical vorticity
+ *     on the 2-PVU surface;
+ *   inputs the host sets, mesh pool, as mpas_initialize_vectors leaves them: cellTangentPlane
+ *     (3, 2, nCells+1), localVerticalUnitVectors (3, nCells+1), edgeNormalVectors (3, nEdges+1).
+ * They are allocated, zeroed, at the first mpas_dyc_set_field of one of them or at mpas_dyc_set_pv(on) --
+ * a context that asks for neither holds none of them (mpas_dyc_field_bytes returns 0) and behaves as
+ * before.  diag.theta and diag.rho exist already; the call rewrites them on the cells 1..nCells.
+ * mpas_dyc_set_pv(on): the switch of mpas_dyc_pv_diagnostics.  On a MPAS_DYC_HOST_ONLY context it is kept
+ * and nothing is allocated. */
+int mpas_dyc_set_pv(mpas_dyc_ctx* ctx, int32_t on);
+/* atm_compute_pv_diagnostics(state, time_level, diag, mesh) (:1218-1289) of every block:
+ *   1. theta = theta_m / (1 + rvord qv), rho = rho_zz zz on all cells of the block (:1253-1258);
+ *   2. on a context that has exchange lists, the halos of diag.theta, uReconstructX/Y/Z and of w of
+ *      time_level (:1270-1274), as mpas_dyc_halo_exchange does: the call is COLLECTIVE across ranks;
+ *   3. ertel_pv on the owned cells (calc_epv, :1139-1216): the finite-volume gradients of w and theta over
+ *      the cell's edges, centred vertical differences (one-sided at the column's ends), the cell's
+ *      vertical vorticity as the kite-area average of diag.vorticity, the Earth's vorticity, divided by
+ *      rho, dotted with grad theta, times 1e6;
+ *   4. the halo of ertel_pv (:1279-1280);
+ *   5. floodFill_tropo (:581-716) over all cells of the block: the cell-levels with ertel_pv sign(lat) < 2
+ *      connected to levels 1..min(nVertLevels, 3) through vertical and same-level horizontal neighbours.
+ *      That set is the fixed point of the reference's sweeps whatever their order.  A neighbour outside
+ *      the block is never in the troposphere, and there is no communication inside the fill: the
+ *      reference's behaviour (its :696), so a block's halo columns may differ from their owners';
+ *   6. iLev_DT on the cells 1..nCells; 7. interp_pv (:826-899) of the four fields on the owned cells.
+ * Halo cells and garbage slots of the four 2-D fields, and iLev_DT's garbage slot, keep what they hold.
+ * It reads w, theta_m, rho_zz and scalars(index_qv) of time_level (1 or 2; the reference passes 1), and
+ * diag.vorticity and uReconstructX/Y/Z/Zonal/Meridional as the last step left them; mesh.zgrid, zz, latCell,
+ * dvEdge, areaCell, kiteAreasOnVertex, the connectivity and the three vector arrays.  fp64 in the Fortran's
+ * operand order, no contraction: every output has the reference's bits, with one defined deviation -- at
+ * level nVertLevels the reference forms dv_dz from velCellp, a local it never set there (:997), so its
+ * ertel_pv(nVertLevels, :) is undefined; this library takes velCellm, as the u line two above it does.
+ * The PV budget (calc_pvBudget, depv_dt_*) needs the physics suites' tendencies and stays with the host;
+ * floodFill_strato, which the reference never calls, is not provided.
+ * SYNCHRONOUS: the fill's sweeps run in small batches and the host reads a flag back after each, so the
+ * call returns with the outputs complete.  Always eager, never part of the step's captured graph, which
+ * stays as it is.  Under mpas_dyc_set_profile its milliseconds are mpas_dyc_get_profile out[9].
+ * Switch off (mpas_dyc_set_pv(0), or never set): does nothing.  MPAS_DYC_EINVAL: time_level other than 1
+ * or 2.  MPAS_DYC_ESTATE: a MPAS_DYC_HOST_ONLY context; between mpas_dyc_timestep and
+ * mpas_dyc_finish_step with MPAS_DYC_PHYSICS_MICROPHYSICS; a needed mesh input never set (the three vector
+ * arrays, areaCell, kiteAreasOnVertex, cellsOnVertex), with a message that names it. */
+int mpas_dyc_pv_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level);
 /* Regional lateral boundary conditions, config_apply_lbcs (mpas_atm_time_integration.F:683-778,
  * 934-987, 1109-1180, 1253-1270, 1491-1560, 1672-1790; the routines at 6088-6671).  apply = 1 turns
  * them on (the pair kernel layout is required).  The host sets, as in the reference's lbc pool
@@ -613,7 +661,10 @@ double mpas_dyc_acoustic_bytes(const mpas_dyc_ctx* ctx);
  * launches on the compute stream; that call is synchronous).
  * out[7] = the same for the last mpas_dyc_microphysics called with the profile on.
  * out[8] = the same for the last mpas_dyc_isobaric_diagnostics called with the profile on (written
- * only when n covers it, like every slot). */
+ * only when n covers it, like every slot).
+ * out[9] = the same for the last mpas_dyc_pv_diagnostics called with the profile on (its read-backs
+ * included); out[10] = the sweeps of the last mpas_dyc_pv_diagnostics' fill that changed something, the
+ * most over the blocks. */
 int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on);
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n);
 /* The plan key of the exchange whose RCCL group was enqueued last ("warm_rccl <key>" while the

@@ -35,6 +35,7 @@
 #include "convdiag.hip"
 #include "kessler.hip"
 #include "isobaric.hip"
+#include "pv.hip"
 
 using namespace mpas;
 
@@ -47,7 +48,7 @@ enum Target { T_NONE, T_CELL, T_EDGE, T_VERTEX, T_SMALL };  // int index semanti
 // coefficients read (mpas_dyc_model_init, mpas_dyc_init_reconstruct).  The others belong to a step hook
 // (physics_host.hip) and are allocated together, zeroed, by alloc_group: when the hook is switched on,
 // or at the first set_field of one of them.
-enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP, G_ISOBARIC };
+enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP, G_ISOBARIC, G_PV };
 // all_blocks: a first set_field completes the group on every block (false: on that block only).
 // hidden: mpas_dyc_block_field_bytes reports 0 until the field is allocated -- the fields are held
 // only by a context that asked for them.
@@ -58,6 +59,7 @@ constexpr struct { bool all_blocks, hidden; } GROUPS[] = {
     {true, false},   // G_CONVDIAG: the convective running maxima
     {true, true},    // G_MICROP: the device microphysics' own fields
     {true, true},    // G_ISOBARIC: the isobaric diagnostics' outputs, level tables and diag.relhum
+    {true, true},    // G_PV: the PV diagnostics' outputs and the three mesh vector arrays they read
 };
 
 struct Field {
@@ -112,6 +114,7 @@ struct Block {
   ConvDiagTable cv;
   bool kite_set = false;               // mesh.kiteAreasOnVertex has been set (the isobaric vorticity reads it)
   int* iso_fail = nullptr;             // compute_slp's failure word of the block (isobaric.hip), on the device
+  PvBlock pv;                          // the PV diagnostics' derived table and fill buffers (pv.hip)
   // maxEdges / maxEdges2 as the host declared them (the mesh file's dimensions; Fortran images and
   // h_eoc use these strides).  d.maxEdges / d.maxEdges2 are the strides the kernels index with:
   // max(nEdgesOnCell) and the edgesOnEdge slots the kernels need after pack_mesh
@@ -304,6 +307,7 @@ struct mpas_dyc_ctx {
   // the step hooks (physics_host.hip), each with its state struct next to its kernels
   IauState iau;                         // incremental analysis update (mpas_dyc_set_iau; iau.hip)
   IsoState iso;                         // the isobaric diagnostics (mpas_dyc_set_isobaric; isobaric.hip)
+  PvState pv;                           // the PV diagnostics (mpas_dyc_set_pv; pv.hip)
   ConvDiagState convdiag;               // the convective running maxima (mpas_dyc_set_diag_update; convdiag.hip)
   MicropState microp;                   // the device microphysics (mpas_dyc_set_microphysics; kessler.hip)
   int64_t graph_captures = 0;           // steps captured so far (mpas_dyc_get_profile out[5])
@@ -571,6 +575,17 @@ void build_registry(Block& c) {
   add(c, "diag", "t_iso_levels", L_NONE, ISO_NT).group = G_ISOBARIC;
   add(c, "diag", "z_iso_levels", L_NONE, ISO_NZ).group = G_ISOBARIC;
   add(c, "diag", "relhum", L_CELL, K).group = G_ISOBARIC;
+  // the PV diagnostics (Registry_pv.xml, diag): ertel_pv (K, nCells + 1), iLev_DT (int, nCells + 1), u_pv,
+  // v_pv, theta_pv, vort_pv (nCells + 1), and the mesh vectors of mpas_initialize_vectors they read, which
+  // the host sets: cellTangentPlane (3, 2, nCells + 1), localVerticalUnitVectors (3, nCells + 1),
+  // edgeNormalVectors (3, nEdges + 1); allocated, zeroed, at the first set_field of one of them or at
+  // mpas_dyc_set_pv(on)
+  add(c, "diag", "ertel_pv", L_CELL, K).group = G_PV;
+  add(c, "diag", "iLev_DT", L_CELL, 1, 1, true).group = G_PV;
+  for (const char* n : {"u_pv", "v_pv", "theta_pv", "vort_pv"}) add(c, "diag", n, L_CELL, 1).group = G_PV;
+  add(c, "mesh", "cellTangentPlane", L_CELL, 6).group = G_PV;
+  add(c, "mesh", "localVerticalUnitVectors", L_CELL, 3).group = G_PV;
+  add(c, "mesh", "edgeNormalVectors", L_EDGE, 3).group = G_PV;
   // the maxEdges- and maxEdges2-strided mesh arrays (pack_mesh)
   for (const char* n : {"edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "coeffs_reconstruct",
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
@@ -586,6 +601,16 @@ bool rec_input(const Field& f) {
                         "fVertex", "kiteAreasOnVertex"})
     if (f.name == n) return true;
   return false;
+}
+
+// A mesh field takes a new image (or a caller may write through its pointer): the PV diagnostics' table
+// (pv.hip k_pv_geom) is built again, and the group's own mesh inputs count as set
+void pv_touch(Block& b, const Field& f) {
+  if (f.pool != "mesh") return;
+  b.pv.ready = false;
+  if (f.name == "cellTangentPlane") b.pv.set |= PV_SET_TANGENT;
+  if (f.name == "localVerticalUnitVectors") b.pv.set |= PV_SET_VERTICAL;
+  if (f.name == "edgeNormalVectors") b.pv.set |= PV_SET_NORMALS;
 }
 
 Field* find(Block& b, const char* pool, const char* name) {
@@ -941,6 +966,7 @@ int compute_bnd(mpas_dyc_ctx* ctx) {
       return MPAS_DYC_ESTATE;
     }
     CHK(pack_mesh(ctx, b));
+    b.pv.ready = false;  // the table is indexed with the packed stride
     if (group_ready(ctx, G_CONVDIAG) && !b.cv.ready) CHK(convdiag_table(ctx, b));
     if (ctx->lbc && !pair_layout(d)) {
       ctx->err = lbc_layout_error(d);
@@ -2643,6 +2669,8 @@ void mpas_dyc_destroy(mpas_dyc_ctx* ctx) {
     if (b.cv.start) (void)hipFree(b.cv.start);
     if (b.cv.kite) (void)hipFree(b.cv.kite);
     if (b.iso_fail) (void)hipFree(b.iso_fail);
+    for (void* q : {(void*)b.pv.geom, (void*)b.pv.cand, (void*)b.pv.mem[0], (void*)b.pv.mem[1], (void*)b.pv.flags})
+      if (q) (void)hipFree(q);
   }
   if (ctx->sum_gather) (void)hipFree(ctx->sum_gather);
   p2p_teardown(ctx);  // after the plans (invalidate_plans above) and the field buffers: see there
@@ -2687,6 +2715,7 @@ void* mpas_dyc_block_field_device_ptr(mpas_dyc_ctx* ctx, int32_t block, const ch
   if (f->me || rec_input(*f) || (f->pool == "mesh" && (f->name == "zb_cell" || f->name == "zb3_cell")))
     ctx->bnd_ready = false;
   coefs_touched(ctx, *f);
+  pv_touch(*b, *f);
   if (f->pool == "mesh" && f->name == "kiteAreasOnVertex") b->kite_set = true;  // a caller may write through it
   return f->buf[slot_of(ctx, *f, time_level)];
 }
@@ -2729,6 +2758,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
                              : alloc_group(ctx, f->group, GROUPS[f->group].all_blocks ? nullptr : &b));
   if (f->me || rec_input(*f)) ctx->bnd_ready = false;  // pack_mesh copies the new image for the kernels
   coefs_touched(ctx, *f);
+  pv_touch(b, *f);
   if (f->is_int && f->target != T_NONE) {
     // MPAS 1-based -> device 0-based; out-of-range / 0 -> garbage slot
     const int64_t n = field_elems(b, *f);
@@ -3579,7 +3609,7 @@ int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on) {
 
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n) {
   if (!ctx || !out || n < 1) return MPAS_DYC_EINVAL;
-  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : i == 8 ? ctx->iso.ms : 0.0;
+  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : i == 8 ? ctx->iso.ms : i == 9 ? ctx->pv.ms : i == 10 ? (double)ctx->pv.sweeps : 0.0;
   return MPAS_DYC_OK;
 }
 

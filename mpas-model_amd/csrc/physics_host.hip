@@ -1,8 +1,9 @@
 // Host side of the step's physics hooks: the incremental analysis update (kernels: iau.hip), the
-// convective running maxima (convdiag.hip), the device microphysics (kessler.hip) and the isobaric output
-// diagnostics (isobaric.hip; not part of the step, but a hook of the same shape).  Per hook: what
+// convective running maxima (convdiag.hip), the device microphysics (kessler.hip), the isobaric output
+// diagnostics (isobaric.hip) and the PV diagnostics (pv.hip; the last two are not part of the step, but
+// hooks of the same shape).  Per hook: what
 // enqueues its kernels, and its entry points of include/mpas_dycore.h.  A hook's state struct
-// (mpas_dyc_ctx::iau / convdiag / microp, Block::cv) stands next to its kernels' argument struct; its
+// (mpas_dyc_ctx::iau / convdiag / microp / iso / pv, Block::cv / pv) stands next to its kernels' argument struct; its
 // fields are a Group of the registry (dycore.hip build_registry), allocated by alloc_group.
 //
 // Included by dycore.hip inside its namespace, before srk3: after the structs (Field, Block,
@@ -219,9 +220,206 @@ int iso_enqueue(mpas_dyc_ctx* ctx, int tl) {
   return MPAS_DYC_OK;
 }
 
+// ---- Ertel PV and dynamic-tropopause diagnostics ----
+// a needed mesh input of block b that was never set, or nullptr
+const char* pv_missing_input(Block& b) {
+  if (!(b.pv.set & PV_SET_TANGENT)) return "mesh.cellTangentPlane";
+  if (!(b.pv.set & PV_SET_VERTICAL)) return "mesh.localVerticalUnitVectors";
+  if (!(b.pv.set & PV_SET_NORMALS)) return "mesh.edgeNormalVectors";
+  if (!find(b, "mesh", "areaCell")->buf[0]) return "mesh.areaCell";
+  if (!b.kite_set) return "mesh.kiteAreasOnVertex";
+  if ((int64_t)b.h_cov.size() < 3LL * b.d.nVertices) return "mesh.cellsOnVertex";
+  return nullptr;
+}
+
+// The block's derived table (k_pv_geom) and its fill buffers, for the mesh arrays and strides as they are
+int pv_prepare(mpas_dyc_ctx* ctx, Block& b) {
+  const Dims& d = b.d;
+  const int64_t geom_n = (int64_t)std::max(1, d.nCellsSolve) * (PV_HDR + 3 * d.maxEdges);
+  const int64_t words_n = (int64_t)((d.K + 63) / 64) * (d.nCells + 1);
+  if (b.pv.geom_n != geom_n || b.pv.words_n != words_n) {
+    HIPCHK(hipStreamSynchronize(ctx->stream));  // a running call still reads the old buffers
+    for (void** q : {(void**)&b.pv.geom, (void**)&b.pv.cand, (void**)&b.pv.mem[0], (void**)&b.pv.mem[1]}) {
+      if (*q) (void)hipFree(*q);
+      *q = nullptr;
+    }
+    b.pv.geom_n = b.pv.words_n = 0;
+    HIPCHK(hipMalloc(&b.pv.geom, geom_n * 8));
+    HIPCHK(hipMalloc(&b.pv.cand, words_n * 8));
+    HIPCHK(hipMalloc(&b.pv.mem[0], words_n * 8));
+    HIPCHK(hipMalloc(&b.pv.mem[1], words_n * 8));
+    b.pv.geom_n = geom_n, b.pv.words_n = words_n;
+    b.pv.ready = false;
+  }
+  if (!b.pv.flags) HIPCHK(hipMalloc(&b.pv.flags, PV_BATCH * sizeof(int)));
+  if (b.pv.ready) return MPAS_DYC_OK;
+  // the garbage slot's words stay 0: no kernel writes them
+  for (unsigned long long* q : {b.pv.cand, b.pv.mem[0], b.pv.mem[1]}) HIPCHK(hipMemsetAsync(q, 0, words_n * 8, ctx->stream));
+  if (d.nCellsSolve > 0) {
+    PvGeomArgs a{};
+    a.nCellsSolve = d.nCellsSolve, a.ME = d.maxEdges;
+    a.nEdgesOnCell = P<const int>(ctx, b, "mesh", "nEdgesOnCell");
+    a.edgesOnCell = P<const int>(ctx, b, "mesh", "edgesOnCell");
+    a.verticesOnCell = P<const int>(ctx, b, "mesh", "verticesOnCell");
+    a.cellsOnEdge = P<const int>(ctx, b, "mesh", "cellsOnEdge");
+    a.cellsOnVertex = P<const int>(ctx, b, "mesh", "cellsOnVertex");
+    a.cellTangentPlane = P<const double>(ctx, b, "mesh", "cellTangentPlane");
+    a.localVerticalUnitVectors = P<const double>(ctx, b, "mesh", "localVerticalUnitVectors");
+    a.edgeNormalVectors = P<const double>(ctx, b, "mesh", "edgeNormalVectors");
+    a.dvEdge = P<const double>(ctx, b, "mesh", "dvEdge");
+    a.areaCell = P<const double>(ctx, b, "mesh", "areaCell");
+    a.kiteAreasOnVertex = P<const double>(ctx, b, "mesh", "kiteAreasOnVertex");
+    a.geom = b.pv.geom;
+    hipLaunchKernelGGL(k_pv_geom, dim3((unsigned)((d.nCellsSolve + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+  }
+  b.pv.ready = true;
+  return MPAS_DYC_OK;
+}
+
+// floodFill_tropo of one block: the candidates and seeds, then sweeps in batches of PV_BATCH until one
+// changes nothing (the host reads the batch's flags back: synchronous), at most nCells + 1 of them.
+// Returns in `members` the buffer that holds the fixed point.
+int pv_fill(mpas_dyc_ctx* ctx, Block& b, const unsigned long long** members, int* sweeps) {
+  const Dims& d = b.d;
+  const int words = (d.K + 63) / 64;
+  hipLaunchKernelGGL(k_pv_cand, dim3((unsigned)((d.nCells + PV_WAVES - 1) / PV_WAVES)), dim3(PV_THREADS), 0, ctx->stream,
+                     d.nCells, d.K, words, P<const double>(ctx, b, "mesh", "latCell"),
+                     P<const double>(ctx, b, "diag", "ertel_pv"), b.pv.cand, b.pv.mem[0]);
+  int src = 0;
+  *sweeps = 0;
+  for (int64_t done = 0; done <= d.nCells;) {
+    HIPCHK(hipMemsetAsync(b.pv.flags, 0, PV_BATCH * sizeof(int), ctx->stream));
+    const int n = (int)std::min<int64_t>(PV_BATCH, (int64_t)d.nCells + 1 - done);
+    for (int i = 0; i < n; ++i, src ^= 1)
+      hipLaunchKernelGGL(k_pv_sweep, dim3((unsigned)((d.nCells + 255) / 256)), dim3(256), 0, ctx->stream, d.nCells, words,
+                         d.maxEdges, P<const int>(ctx, b, "mesh", "nEdgesOnCell"), P<const int>(ctx, b, "mesh", "cellsOnCell"),
+                         (const unsigned long long*)b.pv.cand, (const unsigned long long*)b.pv.mem[src], b.pv.mem[src ^ 1],
+                         b.pv.flags + i);
+    HIPCHK(hipGetLastError());
+    int h[PV_BATCH] = {};
+    HIPCHK(hipMemcpyAsync(h, b.pv.flags, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    done += n;
+    bool fixed = false;
+    for (int i = 0; i < n && !fixed; ++i) {
+      if (h[i]) ++*sweeps;
+      else fixed = true;  // the later sweeps of the batch copied the fixed point
+    }
+    if (fixed) break;
+  }
+  *members = b.pv.mem[src];
+  return MPAS_DYC_OK;
+}
+
+// atm_compute_pv_diagnostics on time level tl of every block (pv.hip), `lists`: with its halo exchanges
+int pv_run(mpas_dyc_ctx* ctx, int tl, bool lists) {
+  const int layers = 7;
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    const int64_t n = (int64_t)d.nCells * d.K;
+    if (n <= 0) continue;
+    hipLaunchKernelGGL(k_pv_theta_rho, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65536)), dim3(256), 0, ctx->stream, n,
+                       P<const double>(ctx, b, "state", "theta_m", tl),
+                       P<const double>(ctx, b, "state", "scalars", tl) + (int64_t)ctx->index_qv * (d.nCells + 1) * d.K,
+                       P<const double>(ctx, b, "state", "rho_zz", tl), P<const double>(ctx, b, "mesh", "zz"),
+                       P<double>(ctx, b, "diag", "theta"), P<double>(ctx, b, "diag", "rho"));
+  }
+  HIPCHK(hipGetLastError());
+  if (lists) {  // :1270-1274
+    for (const char* n : {"theta", "uReconstructX", "uReconstructY", "uReconstructZ"})
+      CHK(mpas_dyc_halo_exchange(ctx, "diag", n, 1, layers));
+    CHK(mpas_dyc_halo_exchange(ctx, "state", "w", tl, layers));
+  }
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    if (d.nCellsSolve <= 0) continue;
+    PvEpv a{};
+    a.nCellsSolve = d.nCellsSolve, a.K = d.K, a.ME = d.maxEdges;
+    a.nEdgesOnCell = P<const int>(ctx, b, "mesh", "nEdgesOnCell");
+    a.cellsOnCell = P<const int>(ctx, b, "mesh", "cellsOnCell");
+    a.verticesOnCell = P<const int>(ctx, b, "mesh", "verticesOnCell");
+    a.geom = b.pv.geom;
+    a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
+    a.w = P<const double>(ctx, b, "state", "w", tl);
+    a.theta = P<const double>(ctx, b, "diag", "theta");
+    a.rho = P<const double>(ctx, b, "diag", "rho");
+    a.vorticity = P<const double>(ctx, b, "diag", "vorticity");
+    a.ux = P<const double>(ctx, b, "diag", "uReconstructX");
+    a.uy = P<const double>(ctx, b, "diag", "uReconstructY");
+    a.uz = P<const double>(ctx, b, "diag", "uReconstructZ");
+    a.ertel_pv = P<double>(ctx, b, "diag", "ertel_pv");
+    hipLaunchKernelGGL(k_pv_epv, dim3((unsigned)((d.nCellsSolve + PV_WAVES - 1) / PV_WAVES)), dim3(PV_THREADS), 0, ctx->stream,
+                       a);
+  }
+  HIPCHK(hipGetLastError());
+  if (lists) CHK(mpas_dyc_halo_exchange(ctx, "diag", "ertel_pv", 1, layers));  // :1279-1280
+  ctx->pv.sweeps = 0;
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    if (d.nCells <= 0) continue;
+    const unsigned long long* members = nullptr;
+    int sweeps = 0;
+    CHK(pv_fill(ctx, b, &members, &sweeps));
+    ctx->pv.sweeps = std::max(ctx->pv.sweeps, sweeps);
+    PvInterp a{};
+    a.nCells = d.nCells, a.nCellsSolve = d.nCellsSolve, a.K = d.K, a.ME = d.maxEdges, a.words = (d.K + 63) / 64;
+    a.nEdgesOnCell = P<const int>(ctx, b, "mesh", "nEdgesOnCell");
+    a.verticesOnCell = P<const int>(ctx, b, "mesh", "verticesOnCell");
+    a.mem = members;
+    a.geom = b.pv.geom;
+    a.latCell = P<const double>(ctx, b, "mesh", "latCell");
+    a.ertel_pv = P<const double>(ctx, b, "diag", "ertel_pv");
+    a.uzonal = P<const double>(ctx, b, "diag", "uReconstructZonal");
+    a.umeridional = P<const double>(ctx, b, "diag", "uReconstructMeridional");
+    a.theta = P<const double>(ctx, b, "diag", "theta");
+    a.vorticity = P<const double>(ctx, b, "diag", "vorticity");
+    a.iLev_DT = P<int>(ctx, b, "diag", "iLev_DT");
+    a.u_pv = P<double>(ctx, b, "diag", "u_pv");
+    a.v_pv = P<double>(ctx, b, "diag", "v_pv");
+    a.theta_pv = P<double>(ctx, b, "diag", "theta_pv");
+    a.vort_pv = P<double>(ctx, b, "diag", "vort_pv");
+    hipLaunchKernelGGL(k_pv_interp, dim3((unsigned)((d.nCells + 255) / 256)), dim3(256), 0, ctx->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return MPAS_DYC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mpas_dyc_set_pv(mpas_dyc_ctx* ctx, int32_t on) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  ctx->pv.on = on ? 1 : 0;
+  if (ctx->host_only || !on) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!group_ready(ctx, G_PV)) CHK(alloc_group(ctx, G_PV));
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_pv_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level) {
+  if (!ctx || (time_level != 1 && time_level != 2)) return MPAS_DYC_EINVAL;
+  CHK(require_device(ctx));
+  if (ctx->tail_pending) {
+    ctx->err = "mpas_dyc_pv_diagnostics between mpas_dyc_timestep and mpas_dyc_finish_step";
+    return MPAS_DYC_ESTATE;
+  }
+  if (!ctx->pv.on) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!group_ready(ctx, G_PV)) CHK(alloc_group(ctx, G_PV));
+  bool lists = false;
+  for (auto& b : ctx->blk) {
+    if (const char* missing = pv_missing_input(b)) {
+      ctx->err = std::string("mpas_dyc_pv_diagnostics: ") + missing + " not set";
+      return MPAS_DYC_ESTATE;
+    }
+    lists = lists || !b.xl.empty();
+  }
+  if (!ctx->bnd_ready) CHK(compute_bnd(ctx));  // the packed strides the table is indexed with
+  for (auto& b : ctx->blk) CHK(pv_prepare(ctx, b));
+  return timed_on_stream(ctx, ctx->pv.ms, [&]() -> int { return pv_run(ctx, time_level, lists); });
+}
 
 int mpas_dyc_set_isobaric(mpas_dyc_ctx* ctx, int32_t flags) {
   if (!ctx) return MPAS_DYC_EINVAL;

@@ -265,6 +265,16 @@ module atm_time_integration
          type(c_ptr), value :: ctx
          integer(c_int32_t), value :: time_level
       end function
+      integer(c_int) function mpas_dyc_set_pv(ctx, on) bind(C, name='mpas_dyc_set_pv')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: on
+      end function
+      integer(c_int) function mpas_dyc_pv_diagnostics(ctx, time_level) bind(C, name='mpas_dyc_pv_diagnostics')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: time_level
+      end function
       integer(c_int) function mpas_dyc_set_summary(ctx, flags) bind(C, name='mpas_dyc_set_summary')
          import :: c_int, c_ptr, c_int32_t
          type(c_ptr), value :: ctx
@@ -324,6 +334,10 @@ module atm_time_integration
    ! the host's arrays of the running maxima were overwritten with the device's (pools_to_host) after
    ! the device's last update: only then does a host array of zeros say anything about a reset
    logical, save, private :: diag_host_current = .false.
+   ! the PV diagnostics (atm_dycore_pv_diagnostics): their mesh vectors and areaCell are on the device
+   logical, save, private :: pv_mesh_sent = .false.
+   character(len=32), dimension(6), parameter, private :: pv_outputs = [character(len=32) :: &
+      'ertel_pv', 'iLev_DT', 'u_pv', 'v_pv', 'theta_pv', 'vort_pv']
    character(len=32), dimension(3), parameter, private :: diag_max_names = [character(len=32) :: &
       'w_velocity_max', 'wind_speed_level1_max', 'updraft_helicity_max']   ! bit i-1 of the mask
    ! the isobaric diagnostics (atm_dycore_isobaric_diagnostics): the groups of six pressure levels in the
@@ -619,6 +633,48 @@ module atm_time_integration
          block => block % next
       end do
    end subroutine atm_dycore_isobaric_diagnostics
+
+   ! atm_compute_pv_diagnostics(state, 1, diag, mesh) (diagnostics/pv_diagnostics.F:1218-1289) on the
+   ! device: what a host's pv_diagnostics_compute calls in its place, after the time levels were shifted.
+   ! The first call uploads the mesh vectors of mpas_initialize_vectors (cellTangentPlane,
+   ! localVerticalUnitVectors, edgeNormalVectors) and areaCell; every call runs mpas_dyc_pv_diagnostics on
+   ! time level 1 and downloads ertel_pv, iLev_DT, u_pv, v_pv, theta_pv and vort_pv into the diag pool.
+   ! The 3-D state stays on the device.  The call exchanges halos: every task calls it.  The PV budget
+   ! (atm_compute_pvBudget_diagnostics) needs the physics' tendencies and stays with the host.
+   subroutine atm_dycore_pv_diagnostics(domain)
+      type (domain_type), intent(inout) :: domain
+      type (block_type), pointer :: block
+      type (mpas_pool_type), pointer :: mesh, diag
+      integer :: ib, i
+
+      if (.not. c_associated(dyc)) return
+      call check(dyc, mpas_dyc_set_pv(dyc, 1_c_int32_t), 'mpas_dyc_set_pv')
+      if (.not. pv_mesh_sent) then
+         block => domain % blocklist
+         ib = 0
+         do while (associated(block))
+            call mpas_pool_get_subpool(block % structs, 'mesh', mesh)
+            call xfer(dyc, ib, mesh, 'mesh', 'cellTangentPlane', 1, 1, UP, .true.)
+            call xfer(dyc, ib, mesh, 'mesh', 'localVerticalUnitVectors', 1, 1, UP, .true.)
+            call xfer(dyc, ib, mesh, 'mesh', 'edgeNormalVectors', 1, 1, UP, .true.)
+            call xfer(dyc, ib, mesh, 'mesh', 'areaCell', 1, 1, UP, .true.)
+            ib = ib + 1
+            block => block % next
+         end do
+         pv_mesh_sent = .true.
+      end if
+      call check(dyc, mpas_dyc_pv_diagnostics(dyc, 1_c_int32_t), 'mpas_dyc_pv_diagnostics')
+      block => domain % blocklist
+      ib = 0
+      do while (associated(block))
+         call mpas_pool_get_subpool(block % structs, 'diag', diag)
+         do i = 1, size(pv_outputs)
+            call xfer(dyc, ib, diag, 'diag', trim(pv_outputs(i)), 1, 1, DOWN, .false.)
+         end do
+         ib = ib + 1
+         block => block % next
+      end do
+   end subroutine atm_dycore_pv_diagnostics
 
    ! Copy the device state into the host pools' time level 1 (the current one once the caller
    ! has shifted time levels after the step): prognostics, diagnostics, rthdynten / rqvdynten.

@@ -30,7 +30,8 @@ EXPORTS = (
     "mpas_dyc_init_deriv_two", "mpas_dyc_init_zb", "mpas_dyc_init_reconstruct", "mpas_dyc_comm_check",
     "mpas_dyc_fused_tend_acoustic", "mpas_dyc_set_iau", "mpas_dyc_iau_weight", "mpas_dyc_set_diag_update",
     "mpas_dyc_diag_update", "mpas_dyc_diag_reset", "mpas_dyc_folded_passes", "mpas_dyc_set_microphysics",
-    "mpas_dyc_microphysics", "mpas_dyc_set_isobaric", "mpas_dyc_isobaric_diagnostics",
+    "mpas_dyc_microphysics", "mpas_dyc_set_isobaric", "mpas_dyc_isobaric_diagnostics", "mpas_dyc_set_pv",
+    "mpas_dyc_pv_diagnostics",
 )
 HOST_ONLY = -2  # MPAS_DYC_HOST_ONLY: planner-only context
 PRINT_GLOBAL_MINMAX_VEL, PRINT_DETAILED_MINMAX_VEL, PRINT_GLOBAL_MINMAX_SCA = 1, 2, 4
@@ -146,6 +147,8 @@ def load() -> C.CDLL:
     lib.mpas_dyc_microphysics.argtypes = [vp, dbl, i32]
     lib.mpas_dyc_set_isobaric.argtypes = [vp, i32]
     lib.mpas_dyc_isobaric_diagnostics.argtypes = [vp, i32]
+    lib.mpas_dyc_set_pv.argtypes = [vp, i32]
+    lib.mpas_dyc_pv_diagnostics.argtypes = [vp, i32]
     lib.mpas_dyc_time_acoustic_step.argtypes = [vp, dbl, i32, i32, C.POINTER(dbl), C.POINTER(dbl)]
     lib.mpas_dyc_use_graph.argtypes = [vp, i32]
     lib.mpas_dyc_acoustic_bytes.argtypes = [vp]

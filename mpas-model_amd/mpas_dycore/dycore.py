@@ -38,7 +38,7 @@ _SKIP = set(STATE_INPUTS) | set(DIAG_INPUTS) | {"xCell", "yCell", "zCell", "xEdg
                                                 "meshDensity", "indexToCellID", "deriv_two", "zb", "zb3",
                                                 "w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max",
                                                 *F.MICROP_FIELD, *F.ISO_CELL_FIELDS, *F.ISO_VERTEX_FIELDS,
-                                                *F.ISO_LEVEL_TABLES}
+                                                *F.ISO_LEVEL_TABLES, *F.PV_OUTPUTS, *F.PV_MESH_INPUTS}
 
 
 def _host_allgather_fn(group, nranks: int):
@@ -530,6 +530,55 @@ class Dycore:
         out = (C.c_double * 9)()
         self._check(self.lib.mpas_dyc_get_profile(self.h, out, 9), "get_profile")
         return float(out[8])
+
+    def set_pv(self, on: bool = True):
+        """The switch of pv_diagnostics() (mpas_dyc_set_pv).  On: allocates, zeroed, diag.ertel_pv (K per
+        cell), iLev_DT (int32), u_pv, v_pv, theta_pv, vort_pv and the three mesh vector arrays, which are
+        uploaded here: the case's cellTangentPlane / localVerticalUnitVectors / edgeNormalVectors, or what
+        reconstruct.initialize_vectors (mpas_initialize_vectors) makes of its cell centres; and areaCell,
+        which the step itself never reads.  An edge of a block's outermost halo that lacks one of its cells
+        in the block gets no meaningful normal; no owned cell has such an edge."""
+        self._check(self.lib.mpas_dyc_set_pv(self.h, int(bool(on))), "set_pv")
+        if not on:
+            return
+        from .reconstruct import initialize_vectors
+        for ib, c in enumerate(self.cases):
+            with np.errstate(invalid="ignore"):
+                vec = c if all(n in c for n in F.PV_MESH_INPUTS) else initialize_vectors(c) if "xCell" in c else {}
+            for name in F.PV_MESH_INPUTS:
+                if name in vec:
+                    self.set_raw("mesh", name, to_fortran({**c, name: vec[name]}, name), block=ib)
+            if "areaCell" in c:
+                self.set_raw("mesh", "areaCell", to_fortran(c, "areaCell"), block=ib)
+
+    def pv_diagnostics(self, time_level: int = 1):
+        """atm_compute_pv_diagnostics (pv_diagnostics.F:1218-1289) on every block
+        (mpas_dyc_pv_diagnostics): theta and rho on all cells, ertel_pv on the owned cells, the tropopause
+        level iLev_DT by the flood fill over the block, and u_pv, v_pv, theta_pv, vort_pv on the owned cells,
+        from w, theta_m, rho_zz and qv of ``time_level`` and the vorticity and reconstructed winds the last
+        step left: call it after shift_time_levels().  Synchronous; never part of the step's captured
+        graph.  On blocks that have exchange lists it exchanges the halos of theta, uReconstructX/Y/Z, w and
+        ertel_pv: collective across ranks.  mpas_dycore.pv is its numpy restatement."""
+        self._check(self.lib.mpas_dyc_pv_diagnostics(self.h, int(time_level)), "pv_diagnostics")
+
+    def pv_ms(self, time_level: int = 1) -> float:
+        """Milliseconds of one pv_diagnostics() call between HIP events, the fill's read-backs included
+        (mpas_dyc_get_profile out[9])."""
+        self._check(self.lib.mpas_dyc_set_profile(self.h, 1), "set_profile")
+        try:
+            self.pv_diagnostics(time_level)
+        finally:
+            self._check(self.lib.mpas_dyc_set_profile(self.h, 0), "set_profile")
+        out = (C.c_double * 10)()
+        self._check(self.lib.mpas_dyc_get_profile(self.h, out, 10), "get_profile")
+        return float(out[9])
+
+    def pv_sweeps(self) -> int:
+        """Sweeps of the last pv_diagnostics()' fill that changed something, the most over the blocks
+        (mpas_dyc_get_profile out[10])."""
+        out = (C.c_double * 11)()
+        self._check(self.lib.mpas_dyc_get_profile(self.h, out, 11), "get_profile")
+        return int(out[10])
 
     def finish_step(self, dt: float):
         """The end of atm_srk3 after the host's microphysics (1672-1794); a no-op unless

@@ -48,7 +48,7 @@ LOCATION.update(w_velocity_max="cell", wind_speed_level1_max="cell", updraft_hel
 MICROP_FIELD = {"rainnc": "diag_physics", "rainncv": "diag_physics", "precipw": "diag_physics",
                 "i_rainnc": "diag_physics", "surface_pressure": "diag", "tend_sfc_pressure": "tend"}
 LOCATION.update({n: "cell" for n in MICROP_FIELD})
-INT_FIELDS = {"i_rainnc"}   # int32 on the device, not an index into an element set
+INT_FIELDS = {"i_rainnc", "iLev_DT"}   # int32 on the device, not an index into an element set
 
 # the isobaric diagnostics (mpas_dyc_set_isobaric; diag pool): <group>_<level>hPa per cell, vorticity_*hPa
 # per vertex, mslp, meanT_500_300, t_isobaric (5 per cell), z_isobaric (13 per cell), the host's relhum (K per
@@ -61,6 +61,13 @@ ISO_VERTEX_FIELDS = tuple(f"vorticity_{p}hPa" for p in ISO_HPA)
 ISO_LEVEL_TABLES = ("t_iso_levels", "z_iso_levels")
 LOCATION.update({n: "cell" for n in ISO_CELL_FIELDS})
 LOCATION.update({n: "vertex" for n in ISO_VERTEX_FIELDS})
+
+# the PV diagnostics (mpas_dyc_set_pv): the outputs in the diag pool, one column (ertel_pv) or one value per
+# cell, and the mesh vectors of mpas_initialize_vectors they read
+PV_OUTPUTS = ("ertel_pv", "iLev_DT", "u_pv", "v_pv", "theta_pv", "vort_pv")
+PV_MESH_INPUTS = ("cellTangentPlane", "localVerticalUnitVectors", "edgeNormalVectors")
+LOCATION.update({n: "cell" for n in PV_OUTPUTS + PV_MESH_INPUTS[:2]})
+LOCATION["edgeNormalVectors"] = "edge"
 
 VERTICAL_1D = ("fzm", "fzp", "rdzw", "rdzu", "u_init", "v_init")
 SCALARS_0D = ("cf1", "cf2", "cf3")
