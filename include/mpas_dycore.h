@@ -397,6 +397,64 @@ int mpas_dyc_set_pv(mpas_dyc_ctx* ctx, int32_t on);
  * mpas_dyc_finish_step with MPAS_DYC_PHYSICS_MICROPHYSICS; a needed mesh input never set (the three vector
  * arrays, areaCell, kiteAreasOnVertex, cellsOnVertex), with a message that names it. */
 int mpas_dyc_pv_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level);
+/* The output-time half of the reference's convective diagnostics (diagnostics/convective_diagnostics.F,
+ * Registry_convective.xml), on the device (convcompute.hip): convective_diagnostics_compute (:227-487) with
+ * getcape (:595-1037), so a run that writes cape, cin or the helicities need not copy theta_m, qv, exner,
+ * pressure_p, pressure_base and the reconstructed winds to the host and lift every column there.  One bit
+ * per output, in the order of the reference's list (:285-312); the diag fields have the reference's
+ * names, lower case (cape, cin, lcl, lfc, srh_0_1km, srh_0_3km, uzonal_surface, uzonal_1km, uzonal_6km,
+ * umeridional_surface, umeridional_1km, umeridional_6km, temperature_surface, dewpoint_surface), each
+ * (nCells + 1). */
+#define MPAS_DYC_CONV_CAPE 1
+#define MPAS_DYC_CONV_CIN 2
+#define MPAS_DYC_CONV_LCL 4
+#define MPAS_DYC_CONV_LFC 8
+#define MPAS_DYC_CONV_SRH_0_1KM 16
+#define MPAS_DYC_CONV_SRH_0_3KM 32
+#define MPAS_DYC_CONV_UZONAL_SURFACE 64
+#define MPAS_DYC_CONV_UZONAL_1KM 128
+#define MPAS_DYC_CONV_UZONAL_6KM 256
+#define MPAS_DYC_CONV_UMERIDIONAL_SURFACE 512
+#define MPAS_DYC_CONV_UMERIDIONAL_1KM 1024
+#define MPAS_DYC_CONV_UMERIDIONAL_6KM 2048
+#define MPAS_DYC_CONV_TEMPERATURE_SURFACE 4096
+#define MPAS_DYC_CONV_DEWPOINT_SURFACE 8192
+#define MPAS_DYC_CONV_ALL 16383
+/* mpas_dyc_set_convective(flags): the mask mpas_dyc_convective_diagnostics applies.  Unknown bits:
+ * MPAS_DYC_EINVAL, nothing allocated.  A non-zero mask allocates the fourteen fields, zeroed; so does a
+ * first mpas_dyc_set_field of one of them.  A context that asks for neither holds none of them
+ * (mpas_dyc_field_bytes returns 0) and behaves as before.  On a MPAS_DYC_HOST_ONLY context the mask is
+ * kept and nothing is allocated. */
+int mpas_dyc_set_convective(mpas_dyc_ctx* ctx, int32_t flags);
+/* convective_diagnostics_compute on the cells 1..nCellsSolve of every block; halo cells and the garbage
+ * slot keep what they hold.  The reference's quirks are kept:
+ *   - with any bit set, uzonal_surface, umeridional_surface, temperature_surface and dewpoint_surface are
+ *     written (level 1 of the winds, of theta_m / (1 + rvord qv) * exner, and of Bolton's dewpoint);
+ *   - uzonal / umeridional _1km / _6km (column_height_value at 1000 m and 6000 m above the lowest
+ *     interface) and srh_0_1km / srh_0_3km (storm-relative helicity against Bunkers' right-mover motion,
+ *     negative contributions discounted) are each written only under their own bit;
+ *   - cape and cin (getcape: the most unstable parcel below 500 hPa, pseudoadiabatic, liquid only,
+ *     100 Pa sub-steps) are both written if either bit is set;
+ *   - lcl and lfc are never written: the reference fetches them and never computes them.  Their bits
+ *     only count towards "any".
+ * It reads theta_m and scalars(index_qv) of time_level (1 or 2; the reference passes 1), diag.exner,
+ * pressure_p, pressure_base, uReconstructZonal / Meridional and mesh.zgrid; not diag.relhum, which the
+ * reference fetches and does not use.  fp64 in the Fortran's operand order, no contraction: the nine
+ * outputs that are + - * / and sqrt have the reference's bits; cape, cin and dewpoint_surface pass through
+ * the device library's exp / log / pow and are within the project's parity bound of them (rel Linf 1e-10)
+ * on columns whose branch decisions a 4 ulp drift of those functions does not move.
+ * One defined deviation, BOUNDED WORK: a column's ascent ends, with cape and cin as accumulated so far,
+ * once it has taken 8192 + nVertLevels sub-steps (a column monotone below 8192 hPa never does; real
+ * columns take under a thousand), and int(dp / pinc) counts as at most 2^30; with the reference's own cap
+ * of 100 iterations per sub-step (after which it too returns what it has) the call ends whatever the
+ * inputs are.
+ * Asynchronous on the compute stream, synchronous under mpas_dyc_set_profile (its milliseconds are
+ * mpas_dyc_get_profile out[11]).  Always eager, never part of the step's captured graph.  Not collective:
+ * no halo is read.  Mask 0: does nothing.  MPAS_DYC_EINVAL: time_level other than 1 or 2.
+ * MPAS_DYC_ESTATE: a MPAS_DYC_HOST_ONLY context; between mpas_dyc_timestep and mpas_dyc_finish_step with
+ * MPAS_DYC_PHYSICS_MICROPHYSICS.  (A context without scalars does not exist: mpas_dyc_create refuses
+ * num_scalars < 1, so there is always a qv, as for mpas_dyc_isobaric_diagnostics.) */
+int mpas_dyc_convective_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level);
 /* Regional lateral boundary conditions, config_apply_lbcs (mpas_atm_time_integration.F:683-778,
  * 934-987, 1109-1180, 1253-1270, 1491-1560, 1672-1790; the routines at 6088-6671).  apply = 1 turns
  * them on (the pair kernel layout is required).  The host sets, as in the reference's lbc pool
@@ -664,7 +722,8 @@ double mpas_dyc_acoustic_bytes(const mpas_dyc_ctx* ctx);
  * only when n covers it, like every slot).
  * out[9] = the same for the last mpas_dyc_pv_diagnostics called with the profile on (its read-backs
  * included); out[10] = the sweeps of the last mpas_dyc_pv_diagnostics' fill that changed something, the
- * most over the blocks. */
+ * most over the blocks.
+ * out[11] = milliseconds of the last mpas_dyc_convective_diagnostics called with the profile on. */
 int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on);
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n);
 /* The plan key of the exchange whose RCCL group was enqueued last ("warm_rccl <key>" while the

@@ -36,6 +36,7 @@
 #include "kessler.hip"
 #include "isobaric.hip"
 #include "pv.hip"
+#include "convcompute.hip"
 
 using namespace mpas;
 
@@ -48,7 +49,7 @@ enum Target { T_NONE, T_CELL, T_EDGE, T_VERTEX, T_SMALL };  // int index semanti
 // coefficients read (mpas_dyc_model_init, mpas_dyc_init_reconstruct).  The others belong to a step hook
 // (physics_host.hip) and are allocated together, zeroed, by alloc_group: when the hook is switched on,
 // or at the first set_field of one of them.
-enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP, G_ISOBARIC, G_PV };
+enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP, G_ISOBARIC, G_PV, G_CONVCOMPUTE };
 // all_blocks: a first set_field completes the group on every block (false: on that block only).
 // hidden: mpas_dyc_block_field_bytes reports 0 until the field is allocated -- the fields are held
 // only by a context that asked for them.
@@ -60,6 +61,7 @@ constexpr struct { bool all_blocks, hidden; } GROUPS[] = {
     {true, true},    // G_MICROP: the device microphysics' own fields
     {true, true},    // G_ISOBARIC: the isobaric diagnostics' outputs, level tables and diag.relhum
     {true, true},    // G_PV: the PV diagnostics' outputs and the three mesh vector arrays they read
+    {true, true},    // G_CONVCOMPUTE: cape, cin, the helicities and the surface / 1 km / 6 km fields
 };
 
 struct Field {
@@ -308,6 +310,7 @@ struct mpas_dyc_ctx {
   IauState iau;                         // incremental analysis update (mpas_dyc_set_iau; iau.hip)
   IsoState iso;                         // the isobaric diagnostics (mpas_dyc_set_isobaric; isobaric.hip)
   PvState pv;                           // the PV diagnostics (mpas_dyc_set_pv; pv.hip)
+  ConvState conv;                       // cape, cin, helicity, surface fields (mpas_dyc_set_convective; convcompute.hip)
   ConvDiagState convdiag;               // the convective running maxima (mpas_dyc_set_diag_update; convdiag.hip)
   MicropState microp;                   // the device microphysics (mpas_dyc_set_microphysics; kessler.hip)
   int64_t graph_captures = 0;           // steps captured so far (mpas_dyc_get_profile out[5])
@@ -586,6 +589,10 @@ void build_registry(Block& c) {
   add(c, "mesh", "cellTangentPlane", L_CELL, 6).group = G_PV;
   add(c, "mesh", "localVerticalUnitVectors", L_CELL, 3).group = G_PV;
   add(c, "mesh", "edgeNormalVectors", L_EDGE, 3).group = G_PV;
+  // the output-time convective diagnostics (Registry_convective.xml, diag): cape, cin, lcl, lfc, srh_0_1km,
+  // srh_0_3km, uzonal / umeridional _surface / _1km / _6km, temperature_surface, dewpoint_surface, each
+  // (nCells + 1); allocated, zeroed, at the first set_field of one of them or at mpas_dyc_set_convective
+  for (const char* n : CONV_FIELDS) add(c, "diag", n, L_CELL, 1).group = G_CONVCOMPUTE;
   // the maxEdges- and maxEdges2-strided mesh arrays (pack_mesh)
   for (const char* n : {"edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "coeffs_reconstruct",
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
@@ -3609,7 +3616,7 @@ int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on) {
 
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n) {
   if (!ctx || !out || n < 1) return MPAS_DYC_EINVAL;
-  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : i == 8 ? ctx->iso.ms : i == 9 ? ctx->pv.ms : i == 10 ? (double)ctx->pv.sweeps : 0.0;
+  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : i == 8 ? ctx->iso.ms : i == 9 ? ctx->pv.ms : i == 10 ? (double)ctx->pv.sweeps : i == 11 ? ctx->conv.ms : 0.0;
   return MPAS_DYC_OK;
 }
 

@@ -1,9 +1,9 @@
 // Host side of the step's physics hooks: the incremental analysis update (kernels: iau.hip), the
 // convective running maxima (convdiag.hip), the device microphysics (kessler.hip), the isobaric output
-// diagnostics (isobaric.hip) and the PV diagnostics (pv.hip; the last two are not part of the step, but
-// hooks of the same shape).  Per hook: what
+// diagnostics (isobaric.hip), the PV diagnostics (pv.hip) and the output-time convective diagnostics
+// (convcompute.hip; the last three are not part of the step, but hooks of the same shape).  Per hook: what
 // enqueues its kernels, and its entry points of include/mpas_dycore.h.  A hook's state struct
-// (mpas_dyc_ctx::iau / convdiag / microp / iso / pv, Block::cv / pv) stands next to its kernels' argument struct; its
+// (mpas_dyc_ctx::iau / convdiag / microp / iso / pv / conv, Block::cv / pv) stands next to its kernels' argument struct; its
 // fields are a Group of the registry (dycore.hip build_registry), allocated by alloc_group.
 //
 // Included by dycore.hip inside its namespace, before srk3: after the structs (Field, Block,
@@ -385,9 +385,64 @@ int pv_run(mpas_dyc_ctx* ctx, int tl, bool lists) {
   return MPAS_DYC_OK;
 }
 
+// ---- cape, cin, storm-relative helicity and the surface / 1 km / 6 km fields ----
+// convective_diagnostics_compute with the context's mask on time level tl of every block: the shear and
+// helicity kernel, then the parcel ascent if cape or cin is asked for
+int conv_enqueue(mpas_dyc_ctx* ctx, int tl) {
+  const int flags = ctx->conv.flags;
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    if (d.nCellsSolve <= 0) continue;
+    ConvCompute a{};
+    a.nCellsSolve = d.nCellsSolve, a.K = d.K, a.flags = flags;
+    a.theta_m = P<const double>(ctx, b, "state", "theta_m", tl);
+    a.qv = P<const double>(ctx, b, "state", "scalars", tl) + (int64_t)ctx->index_qv * (d.nCells + 1) * d.K;
+    a.exner = P<const double>(ctx, b, "diag", "exner");
+    a.pressure_p = P<const double>(ctx, b, "diag", "pressure_p");
+    a.pressure_base = P<const double>(ctx, b, "diag", "pressure_base");
+    a.uzonal = P<const double>(ctx, b, "diag", "uReconstructZonal");
+    a.umeridional = P<const double>(ctx, b, "diag", "uReconstructMeridional");
+    a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
+    for (int i = 0; i < CONV_NFIELDS; ++i) a.out[i] = P<double>(ctx, b, "diag", CONV_FIELDS[i]);
+    hipLaunchKernelGGL(k_conv_shear, dim3((unsigned)((d.nCellsSolve + CONV_WAVES - 1) / CONV_WAVES)), dim3(CONV_THREADS), 0,
+                       ctx->stream, a);
+    if (flags & (CONV_CAPE | CONV_CIN))
+      hipLaunchKernelGGL(k_conv_cape, dim3((unsigned)((d.nCellsSolve + CONV_CAPE_THREADS - 1) / CONV_CAPE_THREADS)),
+                         dim3(CONV_CAPE_THREADS), 0, ctx->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return MPAS_DYC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mpas_dyc_set_convective(mpas_dyc_ctx* ctx, int32_t flags) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (flags & ~CONV_ALL) {
+    ctx->err = "mpas_dyc_set_convective: unknown flag bits";
+    return MPAS_DYC_EINVAL;
+  }
+  ctx->conv.flags = flags;
+  if (ctx->host_only || !flags) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!group_ready(ctx, G_CONVCOMPUTE)) CHK(alloc_group(ctx, G_CONVCOMPUTE));
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_convective_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level) {
+  if (!ctx || (time_level != 1 && time_level != 2)) return MPAS_DYC_EINVAL;
+  CHK(require_device(ctx));
+  if (ctx->tail_pending) {
+    ctx->err = "mpas_dyc_convective_diagnostics between mpas_dyc_timestep and mpas_dyc_finish_step";
+    return MPAS_DYC_ESTATE;
+  }
+  if (!ctx->conv.flags) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!group_ready(ctx, G_CONVCOMPUTE)) CHK(alloc_group(ctx, G_CONVCOMPUTE));
+  return timed_on_stream(ctx, ctx->conv.ms, [&]() -> int { return conv_enqueue(ctx, time_level); });
+}
 
 int mpas_dyc_set_pv(mpas_dyc_ctx* ctx, int32_t on) {
   if (!ctx) return MPAS_DYC_EINVAL;

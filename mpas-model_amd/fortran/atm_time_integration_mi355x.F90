@@ -275,6 +275,17 @@ module atm_time_integration
          type(c_ptr), value :: ctx
          integer(c_int32_t), value :: time_level
       end function
+      integer(c_int) function mpas_dyc_set_convective(ctx, flags) bind(C, name='mpas_dyc_set_convective')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: flags
+      end function
+      integer(c_int) function mpas_dyc_convective_diagnostics(ctx, time_level) &
+            bind(C, name='mpas_dyc_convective_diagnostics')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: time_level
+      end function
       integer(c_int) function mpas_dyc_set_summary(ctx, flags) bind(C, name='mpas_dyc_set_summary')
          import :: c_int, c_ptr, c_int32_t
          type(c_ptr), value :: ctx
@@ -338,6 +349,10 @@ module atm_time_integration
    logical, save, private :: pv_mesh_sent = .false.
    character(len=32), dimension(6), parameter, private :: pv_outputs = [character(len=32) :: &
       'ertel_pv', 'iLev_DT', 'u_pv', 'v_pv', 'theta_pv', 'vort_pv']
+   ! the output-time convective diagnostics (atm_dycore_convective_diagnostics): bit i-1 of the MPAS_DYC_CONV_* mask
+   character(len=32), dimension(14), parameter, private :: conv_outputs = [character(len=32) :: &
+      'cape', 'cin', 'lcl', 'lfc', 'srh_0_1km', 'srh_0_3km', 'uzonal_surface', 'uzonal_1km', 'uzonal_6km', &
+      'umeridional_surface', 'umeridional_1km', 'umeridional_6km', 'temperature_surface', 'dewpoint_surface']
    character(len=32), dimension(3), parameter, private :: diag_max_names = [character(len=32) :: &
       'w_velocity_max', 'wind_speed_level1_max', 'updraft_helicity_max']   ! bit i-1 of the mask
    ! the isobaric diagnostics (atm_dycore_isobaric_diagnostics): the groups of six pressure levels in the
@@ -633,6 +648,47 @@ module atm_time_integration
          block => block % next
       end do
    end subroutine atm_dycore_isobaric_diagnostics
+
+   ! convective_diagnostics_compute (diagnostics/convective_diagnostics.F:227-487, with getcape) on the device:
+   ! what a host's mpas_atm_diag_compute calls in its place, after the time levels were shifted.  flags: the
+   ! MPAS_DYC_CONV_* mask of the fields the streams are about to write (MPAS_field_will_be_written, one bit
+   ! per field in the order of the reference's list).  It runs mpas_dyc_convective_diagnostics on time level
+   ! 1 and downloads what the reference would have written into the diag pool: with any bit the four
+   ! *_surface fields, cape and cin together, the 1 km / 6 km fields and the helicities under their own bits;
+   ! lcl and lfc have no values, in the reference either.  The 3-D state stays on the device; no halo is
+   ! read, so a task may call it alone.
+   subroutine atm_dycore_convective_diagnostics(domain, flags)
+      type (domain_type), intent(inout) :: domain
+      integer, intent(in) :: flags
+      type (block_type), pointer :: block
+      type (mpas_pool_type), pointer :: diag
+      integer :: ib, i
+      logical :: written
+
+      if (.not. c_associated(dyc) .or. flags == 0) return
+      call check(dyc, mpas_dyc_set_convective(dyc, int(flags, c_int32_t)), 'mpas_dyc_set_convective')
+      call check(dyc, mpas_dyc_convective_diagnostics(dyc, 1_c_int32_t), 'mpas_dyc_convective_diagnostics')
+      block => domain % blocklist
+      ib = 0
+      do while (associated(block))
+         call mpas_pool_get_subpool(block % structs, 'diag', diag)
+         do i = 1, size(conv_outputs)
+            select case (i)
+            case (1, 2)
+               written = iand(flags, 3) /= 0
+            case (3, 4)
+               written = .false.
+            case (7, 10, 13, 14)
+               written = .true.
+            case default
+               written = iand(flags, ishft(1, i - 1)) /= 0
+            end select
+            if (written) call xfer(dyc, ib, diag, 'diag', trim(conv_outputs(i)), 1, 1, DOWN, .false.)
+         end do
+         ib = ib + 1
+         block => block % next
+      end do
+   end subroutine atm_dycore_convective_diagnostics
 
    ! atm_compute_pv_diagnostics(state, 1, diag, mesh) (diagnostics/pv_diagnostics.F:1218-1289) on the
    ! device: what a host's pv_diagnostics_compute calls in its place, after the time levels were shifted.

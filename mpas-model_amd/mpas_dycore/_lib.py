@@ -31,7 +31,7 @@ EXPORTS = (
     "mpas_dyc_fused_tend_acoustic", "mpas_dyc_set_iau", "mpas_dyc_iau_weight", "mpas_dyc_set_diag_update",
     "mpas_dyc_diag_update", "mpas_dyc_diag_reset", "mpas_dyc_folded_passes", "mpas_dyc_set_microphysics",
     "mpas_dyc_microphysics", "mpas_dyc_set_isobaric", "mpas_dyc_isobaric_diagnostics", "mpas_dyc_set_pv",
-    "mpas_dyc_pv_diagnostics",
+    "mpas_dyc_pv_diagnostics", "mpas_dyc_set_convective", "mpas_dyc_convective_diagnostics",
 )
 HOST_ONLY = -2  # MPAS_DYC_HOST_ONLY: planner-only context
 PRINT_GLOBAL_MINMAX_VEL, PRINT_DETAILED_MINMAX_VEL, PRINT_GLOBAL_MINMAX_SCA = 1, 2, 4
@@ -43,6 +43,11 @@ MICROP_OFF, MICROP_KESSLER = 0, 1
 (ISO_TEMPERATURE, ISO_RELHUM, ISO_DEWPOINT, ISO_UZONAL, ISO_UMERIDIONAL, ISO_HEIGHT, ISO_W, ISO_VORTICITY, ISO_MSLP,
  ISO_T_ISOBARIC, ISO_Z_ISOBARIC, ISO_MEANT_500_300) = (1 << i for i in range(12))
 ISO_ALL = 4095
+# MPAS_DYC_CONV_*: the outputs of mpas_dyc_convective_diagnostics, in the order of the reference's list
+(CONV_CAPE, CONV_CIN, CONV_LCL, CONV_LFC, CONV_SRH_0_1KM, CONV_SRH_0_3KM, CONV_UZONAL_SURFACE, CONV_UZONAL_1KM,
+ CONV_UZONAL_6KM, CONV_UMERIDIONAL_SURFACE, CONV_UMERIDIONAL_1KM, CONV_UMERIDIONAL_6KM, CONV_TEMPERATURE_SURFACE,
+ CONV_DEWPOINT_SURFACE) = (1 << i for i in range(14))
+CONV_ALL = 16383
 CELL, EDGE, VERTEX = 0, 1, 2
 SEND, RECV = 0, 1
 
@@ -149,6 +154,8 @@ def load() -> C.CDLL:
     lib.mpas_dyc_isobaric_diagnostics.argtypes = [vp, i32]
     lib.mpas_dyc_set_pv.argtypes = [vp, i32]
     lib.mpas_dyc_pv_diagnostics.argtypes = [vp, i32]
+    lib.mpas_dyc_set_convective.argtypes = [vp, i32]
+    lib.mpas_dyc_convective_diagnostics.argtypes = [vp, i32]
     lib.mpas_dyc_time_acoustic_step.argtypes = [vp, dbl, i32, i32, C.POINTER(dbl), C.POINTER(dbl)]
     lib.mpas_dyc_use_graph.argtypes = [vp, i32]
     lib.mpas_dyc_acoustic_bytes.argtypes = [vp]

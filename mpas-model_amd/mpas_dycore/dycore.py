@@ -38,7 +38,7 @@ _SKIP = set(STATE_INPUTS) | set(DIAG_INPUTS) | {"xCell", "yCell", "zCell", "xEdg
                                                 "meshDensity", "indexToCellID", "deriv_two", "zb", "zb3",
                                                 "w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max",
                                                 *F.MICROP_FIELD, *F.ISO_CELL_FIELDS, *F.ISO_VERTEX_FIELDS,
-                                                *F.ISO_LEVEL_TABLES, *F.PV_OUTPUTS, *F.PV_MESH_INPUTS}
+                                                *F.ISO_LEVEL_TABLES, *F.PV_OUTPUTS, *F.PV_MESH_INPUTS, *F.CONV_OUTPUTS}
 
 
 def _host_allgather_fn(group, nranks: int):
@@ -579,6 +579,47 @@ class Dycore:
         out = (C.c_double * 11)()
         self._check(self.lib.mpas_dyc_get_profile(self.h, out, 11), "get_profile")
         return int(out[10])
+
+    def set_convective(self, flags: int | None = None, **outputs: bool):
+        """Which outputs convective_diagnostics() computes (mpas_dyc_set_convective; the reference's
+        MPAS_field_will_be_written switches, convective_diagnostics.F:285-312).  ``flags``: the
+        MPAS_DYC_CONV_* mask (default: all), or keyword switches named like the constants of ``_lib``
+        without the prefix, e.g. ``set_convective(cape=True, srh_0_3km=True)``.  A non-zero mask allocates,
+        zeroed, the fourteen diag fields of ``fields.CONV_OUTPUTS``, one value per cell."""
+        if outputs:
+            if flags is not None:
+                raise ValueError("set_convective: either flags or keyword switches")
+            flags = 0
+            for name, on in outputs.items():
+                bit = getattr(_lib, "CONV_" + name.upper(), None)
+                if bit is None or name.upper() == "ALL":
+                    raise ValueError(f"set_convective: unknown output {name!r}")
+                flags |= bit if on else 0
+        elif flags is None:
+            flags = _lib.CONV_ALL
+        self._check(self.lib.mpas_dyc_set_convective(self.h, int(flags)), "set_convective")
+
+    def convective_diagnostics(self, time_level: int = 1):
+        """convective_diagnostics_compute (convective_diagnostics.F:227-487, with getcape) on the owned
+        cells of every block with the mask of set_convective (mpas_dyc_convective_diagnostics), from
+        theta_m and qv of ``time_level``, diag.exner / pressure_p / pressure_base and the reconstructed
+        winds the last step left: call it after shift_time_levels().  With any bit the four *_surface
+        fields are written; cape and cin come together; lcl and lfc are never written (the reference has
+        no values for them).  Asynchronous; never part of the step's captured graph; not collective.
+        mpas_dycore.convcompute is its numpy restatement."""
+        self._check(self.lib.mpas_dyc_convective_diagnostics(self.h, int(time_level)), "convective_diagnostics")
+
+    def convective_diagnostics_ms(self, time_level: int = 1) -> float:
+        """Milliseconds of one convective_diagnostics() call between HIP events (mpas_dyc_get_profile
+        out[11]); synchronous."""
+        self._check(self.lib.mpas_dyc_set_profile(self.h, 1), "set_profile")
+        try:
+            self.convective_diagnostics(time_level)
+        finally:
+            self._check(self.lib.mpas_dyc_set_profile(self.h, 0), "set_profile")
+        out = (C.c_double * 12)()
+        self._check(self.lib.mpas_dyc_get_profile(self.h, out, 12), "get_profile")
+        return float(out[11])
 
     def finish_step(self, dt: float):
         """The end of atm_srk3 after the host's microphysics (1672-1794); a no-op unless

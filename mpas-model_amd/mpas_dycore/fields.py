@@ -69,6 +69,12 @@ PV_MESH_INPUTS = ("cellTangentPlane", "localVerticalUnitVectors", "edgeNormalVec
 LOCATION.update({n: "cell" for n in PV_OUTPUTS + PV_MESH_INPUTS[:2]})
 LOCATION["edgeNormalVectors"] = "edge"
 
+# the output-time convective diagnostics (mpas_dyc_set_convective; diag pool), one value per cell, in the bit
+# order of MPAS_DYC_CONV_*
+CONV_OUTPUTS = ("cape", "cin", "lcl", "lfc", "srh_0_1km", "srh_0_3km", "uzonal_surface", "uzonal_1km", "uzonal_6km",
+                "umeridional_surface", "umeridional_1km", "umeridional_6km", "temperature_surface", "dewpoint_surface")
+LOCATION.update({n: "cell" for n in CONV_OUTPUTS})
+
 VERTICAL_1D = ("fzm", "fzp", "rdzw", "rdzu", "u_init", "v_init")
 SCALARS_0D = ("cf1", "cf2", "cf3")
 
