@@ -270,7 +270,11 @@ int mpas_dyc_diag_reset(mpas_dyc_ctx* ctx, int32_t flags);
  * config_bucket_rainnc (> 0: rainnc above it moves one bucket into i_rainnc).  While on it implies the
  * step of MPAS_DYC_PHYSICS_TENDENCIES, as mpas_dyc_set_iau does and for the same reason (the call sits
  * inside the reference's DO_PHYSICS block), and the step reads tend.rt_diabatic_tend.  Changing the
- * switch drops the captured steps.  MPAS_DYC_EINVAL: an unknown scheme, an index outside
+ * switch drops the captured steps.  MPAS_DYC_MICROP_OFF after steps have run clears nothing:
+ * tend.rt_diabatic_tend keeps the scheme's last values and the following steps go on reading them, as
+ * the reference's do with whatever its microphysics left there -- from then on the field is the host's
+ * to manage, as on the MPAS_DYC_PHYSICS_MICROPHYSICS path (a host that takes the microphysics over
+ * writes it after every step; one that runs none sets it to zero).  MPAS_DYC_EINVAL: an unknown scheme, an index outside
  * 1..num_scalars, two of index_qv / index_qc / index_qr equal; MPAS_DYC_ESTATE: together with
  * MPAS_DYC_PHYSICS_MICROPHYSICS (the host's microphysics), in whichever order the two are set.  On a
  * MPAS_DYC_HOST_ONLY context the switch is kept and nothing is allocated. */

@@ -222,3 +222,118 @@ def regional_lbc(case: dict,interior_deg: float = 40.0, interval_end: float = 10
     lbc["lbc_scalars_s"] = sc * (1.0 + 3.0 * pc[:, :, None])
     lbc["lbc_scalars_t"] = sc * tc[:, :, None]
     return c, lbc
+
+
+def seed_cloud_and_rain(case: dict) -> dict:
+    """A copy of a moist case of ns >= 3 (qv, qc, qr) with cloud and rain seeded in the lower
+    troposphere of every tenth cell: what makes the Kessler scheme's data-dependent sedimentation loop
+    run in a few steps of the JW state."""
+    case = dict(case)
+    n, K, ns = case["nCells"], case["nVertLevels"], case["num_scalars"]
+    sc = np.array(case["scalars"], dtype=np.float64).reshape(n, K, ns)
+    kk = np.arange(K)[None, :]
+    patch = (np.arange(n) % 10 == 0)[:, None]
+    sc[:, :, 1] = np.where(patch & (kk >= 2) & (kk < 10), 1.0e-3, 0.0)
+    sc[:, :, 2] = np.where(patch & (kk >= 1) & (kk < 8), 2.0e-3 * (1.0 + np.sin(np.arange(n)))[:, None], 0.0)
+    case["scalars"] = sc.reshape(np.asarray(case["scalars"]).shape)
+    return case
+
+
+def reference_nearest(case: dict) -> np.ndarray:
+    """nearestRelaxationCell as mpas_atm_setup_bdy_masks computes it (:466-518; 0-based, -1 = none):
+    the nearest mask-5 cell among the neighbours, for row 7 through a row-6 neighbour, so every index
+    lies within two cells of its cell and therefore inside the halo of a block that owns the cell."""
+    mask = np.asarray(case["bdyMaskCell"])
+    coc, noc = np.asarray(case["cellsOnCell"]), np.asarray(case["nEdgesOnCell"])
+    xyz = np.stack([np.asarray(case["xCell"]), np.asarray(case["yCell"]), np.asarray(case["zCell"])], 1)
+    near = np.full(case["nCells"], -1, dtype=np.int64)
+    for c in np.flatnonzero(mask == 6):
+        best = 1.0e36
+        for i in coc[c, :noc[c]]:
+            if mask[i] == 5:
+                d = ((xyz[i] - xyz[c]) ** 2).sum()
+                if d < best:
+                    best, near[c] = d, i
+    for c in np.flatnonzero(mask == 7):
+        best = 1.0e36
+        for i in coc[c, :noc[c]]:
+            if mask[i] != 6:
+                continue
+            for ii in coc[i, :noc[i]]:
+                if mask[ii] == 5:
+                    d = ((xyz[ii] - xyz[c]) ** 2).sum()
+                    if d < best:
+                        best, near[c] = d, ii
+    return near
+
+
+def iau_increments(case: dict) -> dict:
+    """Smooth analysis increments of both signs over every element and level: u_amb ~ 1 m/s,
+    theta_amb ~ 1 K, rho_amb ~ 1e-2, q*_amb ~ 1e-4.  rho_amb has that size where the air is densest and
+    falls off with the base-state density above, as an analysis increment of density does: 1e-2 at the
+    model top, where rho is a few 1e-2, would halve or double the density within the window, and the
+    run (with IAU on the device or with the host's sums alike) leaves the range of the model."""
+    K, ns = case["nVertLevels"], case["num_scalars"]
+    kk = ((np.arange(K) + 0.5) / K)[None, :]
+    latc, lonc = case["latCell"][:, None], case["lonCell"][:, None]
+    late, lone = case["latEdge"][:, None], case["lonEdge"][:, None]
+    sc = np.zeros((case["nCells"], K, ns))
+    for i in range(ns):
+        sc[:, :, i] = 1e-4 * np.sin((i + 2) * lonc + i) * np.cos(latc) * np.cos(np.pi * (i + 1) * kk)
+    rb = case["rho_base"] / np.max(case["rho_base"])
+    return dict(u_amb=np.cos(late) * np.sin(2 * lone + 0.3) * np.cos(np.pi * kk) + 0.25 * np.sin(3 * late),
+                theta_amb=np.sin(2 * latc) * np.cos(lonc) * (1.0 - 2.0 * kk) + 0.3 * np.sin(3 * lonc),
+                rho_amb=1e-2 * rb * np.cos(latc) * np.sin(lonc - 0.7) * np.cos(2 * np.pi * kk), scalars_amb=sc)
+
+
+def physics_forcing(case: dict, scale: float = 1.0) -> dict:
+    """Smooth prescribed physics tendencies (what physics_get_tend hands the dycore,
+    mpas_atm_time_integration.F:424-449): coupled momentum / theta / density tendencies and scalar
+    tendencies of typical magnitude, element-major; the water-vapour tendency is negative aloft so that
+    the clip of negative mixing ratios (1642-1644) is exercised.  The suite's forcing:
+    tests/test_forecast_case.py holds this to the test helper of the same name bit for bit."""
+    K, ns = case["nVertLevels"], case["num_scalars"]
+    kk = (np.arange(K) + 0.5) / K
+    latc, lonc = case["latCell"][:, None], case["lonCell"][:, None]
+    late, lone = case["latEdge"][:, None], case["lonEdge"][:, None]
+    f = dict(
+        tend_ru_physics=scale * 2e-4 * np.cos(late) * np.sin(2 * lone) * (1 - kk),
+        tend_rtheta_physics=scale * 3e-4 * np.cos(latc) ** 2 * np.exp(-3 * kk) * (1 + 0.5 * np.sin(lonc)),
+        tend_rho_physics=scale * 1e-7 * np.sin(latc) * np.cos(lonc) * (1 - kk),
+    )
+    st = np.zeros((case["nCells"], K, ns))
+    for i in range(ns):
+        st[:, :, i] = scale * 1e-7 * np.cos((i + 1) * latc) * np.sin(lonc + i) * (1 - kk) ** (i + 1)
+    st[:, :, 0] -= scale * 5e-7 * kk ** 2
+    f["scalars_tend"] = st
+    return f
+
+
+FORECAST_DT = 600.0
+FORECAST_NS = 3
+
+
+def forecast_case(K: int) -> tuple[dict, dict, dict, dict]:
+    """A regional forecast with every optional part of the step in play, on x1.642 with qv, qc, qr
+    (moist_end = 3) and a step of case["dt"] = 600 s: (case, lbc, increments, physics).
+      case: the moist JW state with cloud and rain seeded (seed_cloud_and_rain), made limited-area by
+        regional_lbc(interior_deg = 120) -- applied after the seeding, so the driving scalars hold qc
+        and qr -- with nearestRelaxationCell as the reference computes it (reference_nearest), so the
+        case can be decomposed.  Every zone is populated: bdyMaskCell 1..7 holds 40 / 34 / 30 / 26 / 18 /
+        12 / 3 cells around 479 interior ones;
+      lbc: regional_lbc's driving data;
+      increments: iau_increments, and "window" = 2.5 dt: three forced steps, then free ones;
+      physics: physics_forcing(case, 0.1), which keeps a run with IAU inside the model's range.
+    Meant to run with the physics forcing and IAU together when the Kessler scheme is on: the JW column
+    reaches 45 km, and on its top levels (the top three of 26) the saturation vapour pressure of the initial
+    state exceeds the pressure, where the scheme's qvs = ep_2 es / (p - es) turns negative and its
+    saturation adjustment heats without bound.  The forcing's drying aloft times Rv/Rd theta in IAU's
+    theta_m tendency cools those levels enough to keep es at or below p; with either left out the top
+    level's theta_m passes 8000 K within four steps (tests/test_gpu_forecast.py::test_each_hook_acts)."""
+    case = seed_cloud_and_rain(jw_case(642, K, ns=FORECAST_NS, moist=True, cache=False))
+    case, lbc = regional_lbc(case, interior_deg=120.0)
+    case["nearestRelaxationCell"] = reference_nearest(case)
+    case["dt"] = FORECAST_DT
+    inc = iau_increments(case)
+    inc["window"] = 2.5 * FORECAST_DT
+    return case, lbc, inc, physics_forcing(case, 0.1)

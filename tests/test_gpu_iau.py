@@ -35,22 +35,9 @@ def _case(K, monotonic):
 
 
 def increments(case):
-    """Smooth analysis increments of both signs over every element and level: u_amb ~ 1 m/s,
-    theta_amb ~ 1 K, rho_amb ~ 1e-2, q*_amb ~ 1e-4.  rho_amb has that size where the air is densest and
-    falls off with the base-state density above, as an analysis increment of density does: 1e-2 at the
-    model top, where rho is a few 1e-2, would halve or double the density within the window, and the
-    run (with IAU on the device or with the host's sums alike) leaves the range of the model."""
-    K, ns = case["nVertLevels"], case["num_scalars"]
-    kk = ((np.arange(K) + 0.5) / K)[None, :]
-    latc, lonc = case["latCell"][:, None], case["lonCell"][:, None]
-    late, lone = case["latEdge"][:, None], case["lonEdge"][:, None]
-    sc = np.zeros((case["nCells"], K, ns))
-    for i in range(ns):
-        sc[:, :, i] = 1e-4 * np.sin((i + 2) * lonc + i) * np.cos(latc) * np.cos(np.pi * (i + 1) * kk)
-    rb = case["rho_base"] / np.max(case["rho_base"])
-    return dict(u_amb=np.cos(late) * np.sin(2 * lone + 0.3) * np.cos(np.pi * kk) + 0.25 * np.sin(3 * late),
-                theta_amb=np.sin(2 * latc) * np.cos(lonc) * (1.0 - 2.0 * kk) + 0.3 * np.sin(3 * lonc),
-                rho_amb=1e-2 * rb * np.cos(latc) * np.sin(lonc - 0.7) * np.cos(2 * np.pi * kk), scalars_amb=sc)
+    """The smooth analysis increments of mpas_dycore.cases.iau_increments (shared with the forecast case)."""
+    from mpas_dycore.cases import iau_increments
+    return iau_increments(case)
 
 
 def iau_terms(wgt, inc, zz, rho_edge, rho_zz, theta_m, scalars, phys):

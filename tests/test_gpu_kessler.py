@@ -204,15 +204,8 @@ def test_second_call_accumulates_and_bucket(golden):
 # ---------------------------------------------------------------------------------------- in the step
 def _seeded(K=26):
     """Moist JW with cloud and rain seeded in the lower troposphere of every tenth cell."""
-    case = dict(_case(K))
-    n = case["nCells"]
-    sc = np.array(case["scalars"], dtype=np.float64).reshape(n, K, NS)
-    kk = np.arange(K)[None, :]
-    patch = (np.arange(n) % 10 == 0)[:, None]
-    sc[:, :, 1] = np.where(patch & (kk >= 2) & (kk < 10), 1.0e-3, 0.0)
-    sc[:, :, 2] = np.where(patch & (kk >= 1) & (kk < 8), 2.0e-3 * (1.0 + np.sin(np.arange(n)))[:, None], 0.0)
-    case["scalars"] = sc.reshape(np.asarray(case["scalars"]).shape)
-    return case
+    from mpas_dycore.cases import seed_cloud_and_rain
+    return seed_cloud_and_rain(_case(K))
 
 
 def _state(dy, block=None):

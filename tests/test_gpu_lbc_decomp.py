@@ -20,38 +20,12 @@ FIELDS = [("state", "u", "edge"), ("state", "theta_m", "cell"), ("state", "rho_z
 NSTEPS = 3
 
 
-def _reference_nearest(case):
-    """nearestRelaxationCell as mpas_atm_setup_bdy_masks computes it (0-based, -1 = none)."""
-    mask = np.asarray(case["bdyMaskCell"])
-    coc, noc = np.asarray(case["cellsOnCell"]), np.asarray(case["nEdgesOnCell"])
-    xyz = np.stack([np.asarray(case["xCell"]), np.asarray(case["yCell"]), np.asarray(case["zCell"])], 1)
-    near = np.full(case["nCells"], -1, dtype=np.int64)
-    for c in np.flatnonzero(mask == 6):
-        best = 1.0e36
-        for i in coc[c, :noc[c]]:
-            if mask[i] == 5:
-                d = ((xyz[i] - xyz[c]) ** 2).sum()
-                if d < best:
-                    best, near[c] = d, i
-    for c in np.flatnonzero(mask == 7):
-        best = 1.0e36
-        for i in coc[c, :noc[c]]:
-            if mask[i] != 6:
-                continue
-            for ii in coc[i, :noc[i]]:
-                if mask[ii] == 5:
-                    d = ((xyz[ii] - xyz[c]) ** 2).sum()
-                    if d < best:
-                        best, near[c] = d, ii
-    return near
-
-
 def _case(moist, K=26):
-    from mpas_dycore.cases import jw_case, regional_lbc
+    from mpas_dycore.cases import jw_case, reference_nearest, regional_lbc
     case = jw_case(2562, K=K, ns=6 if moist else 1, moist=moist, cache=False)
     case, lbc = regional_lbc(case, interior_deg=150.0)
     assert (np.asarray(case["bdyMaskCell"]) == 7).sum() > 0
-    case["nearestRelaxationCell"] = _reference_nearest(case)
+    case["nearestRelaxationCell"] = reference_nearest(case)
     return case, lbc
 
 
