@@ -154,7 +154,12 @@ int mpas_dyc_synchronize(mpas_dyc_ctx* ctx);
  * time level 2, rtheta_p, exner, pressure_p, rt_diabatic_tend), and then calls mpas_dyc_finish_step,
  * which runs what follows the microphysics in atm_srk3: the regional reset of the specified zone
  * (1672-1790, config_apply_lbcs) and summarize_timestep's reductions (1794).  Without this flag
- * mpas_dyc_timestep runs them itself and mpas_dyc_finish_step does nothing. */
+ * mpas_dyc_timestep runs them itself and mpas_dyc_finish_step does nothing.
+ * MPAS_DYC_EINVAL: unknown bits, MPAS_DYC_PHYSICS_RQVDYNTEN without MPAS_DYC_PHYSICS_TENDENCIES.
+ * MPAS_DYC_ESTATE: MPAS_DYC_PHYSICS_MICROPHYSICS with mpas_dyc_set_microphysics on, or
+ * MPAS_DYC_PHYSICS_TENDENCIES with mpas_dyc_set_todynamics on (see there).  On a MPAS_DYC_HOST_ONLY
+ * context the flags are kept (mpas_dyc_plan_exchanges plans the step they describe, and the exclusions
+ * above hold) and nothing else happens. */
 #define MPAS_DYC_PHYSICS_MICROPHYSICS 4
 int mpas_dyc_set_physics(mpas_dyc_ctx* ctx, int32_t flags);
 /* Incremental analysis update: the branch of atm_srk3 after physics_get_tend
@@ -287,6 +292,68 @@ int mpas_dyc_set_microphysics(mpas_dyc_ctx* ctx, int32_t scheme, int32_t index_q
  * with dt_microp = dt on time_level (1 or 2).  Asynchronous on the compute stream (synchronous only
  * while mpas_dyc_set_profile is on, which times it: mpas_dyc_get_profile out[7]). */
 int mpas_dyc_microphysics(mpas_dyc_ctx* ctx, double dt, int32_t time_level);
+/* The coupling of the physics tendencies to the dynamics, physics_get_tend
+ * (physics/mpas_atmphys_todynamics.F:59-434, called at mpas_atm_time_integration.F:424-449), on the device
+ * (todynamics.hip), so a host with PBL, convection or radiation schemes uploads a raw tendency only when a
+ * scheme has produced a new one and never needs the state back for the coupling.  The inputs are the raw
+ * tendencies of the tend_physics pool,
+ *   rublten rvblten rthblten rqvblten rqcblten rqiblten rniblten rucuten rvcuten rthcuten rqvcuten rqccuten
+ *   rqrcuten rqicuten rqscuten rthratenlw rthratensw, each (K, nCells+1),
+ * and mesh.east / mesh.north (3, nCells+1; init_dirs_forphys, mpas_atmphys_init.F:427-439) and
+ * mesh.edgeNormalVectors (3, nEdges+1), which the host sets.  It keeps tend_physics.rublten_Edge /
+ * rucuten_Edge and diag.tend_u_phys, each (K, nEdges+1).  All of these but edgeNormalVectors are allocated,
+ * zeroed, at the first mpas_dyc_set_field of one of them or when the switch goes on -- a context that asks
+ * for neither holds none of them (mpas_dyc_field_bytes returns 0) -- and set_field / get_field /
+ * field_bytes / field_device_ptr work on them from then on.  No buffer rotation of the step touches them:
+ * their device pointers are stable for the life of the context, so a scheme or emulator that lives on
+ * the GPU may write its tendencies through mpas_dyc_field_device_ptr, on the compute stream or ordered
+ * with it.
+ * The results go to the arrays a host that couples by itself uploads (MPAS_DYC_PHYSICS_TENDENCIES):
+ * tend_physics.tend_ru_physics, tend_rtheta_physics, tend_rho_physics (= 0) and tend.scalars_tend, with the
+ * reference's bits (fp64, the Fortran's operand order, no contraction): tend_toEdges (:494-510) on every
+ * edge of the block, each dot product as (n1 e1 + n2 e2) + n3 e3; the mass-weighted sums in the order PBL,
+ * convection, longwave, shortwave (:343-422); the theta_m conversion (:426-432).  Elements outside the
+ * owned range, the garbage slot included, and every plane of scalars_tend that no scheme touches (:178)
+ * are 0.0.  mass is rho_zz of time level 1 (time level 2 has the same bits after
+ * atm_rk_integration_setup), theta_m and scalars are time level 1, rho_edge is the last
+ * atm_compute_solve_diagnostics'.
+ * mpas_dyc_set_todynamics(flags, index_qc, index_qr, index_qi, index_qs, index_ni): non-zero flags make
+ * every mpas_dyc_timestep run the coupling after the moist coefficients and before the IAU add, captured
+ * with the step, and imply the step of MPAS_DYC_PHYSICS_TENDENCIES as mpas_dyc_set_iau does;
+ * MPAS_DYC_TODYN_RQVDYNTEN makes the step compute tend_physics.rqvdynten as MPAS_DYC_PHYSICS_RQVDYNTEN
+ * does.  The indices are the 1-based scalar indices (index_qv is the context's).  An index <= 0 means the
+ * scalar is absent and its terms are skipped -- the reference would index outside the array there.
+ * Reference quirk kept: tend_u_phys is assigned only under the PBL branch (:334), so with the PBL off and a
+ * Tiedtke scheme it accumulates rucuten_Edge from call to call (:393-394).
+ * On blocks with exchange lists the halos of rublten / rvblten (MPAS_DYC_TODYN_PBL) and rucuten / rvcuten
+ * (MPAS_DYC_TODYN_CU_WINDS) are exchanged before the projection (:474-492), as one exchange point of the
+ * step, on every transport; without those flags the step's exchange plan is unchanged.
+ * MPAS_DYC_EINVAL: unknown bits, a sub-flag without its parent (_PBL_MYNN without _PBL; _CU_KF or
+ * _CU_WINDS without _CU), _CU_KF together with _CU_WINDS, an index above num_scalars or equal to
+ * index_qv.  MPAS_DYC_ESTATE: together with MPAS_DYC_PHYSICS_TENDENCIES (the host's coupled arrays), in
+ * whichever order the two are set.  A step, or mpas_dyc_physics_get_tend, with a wind flag on and
+ * mesh.east, mesh.north or mesh.edgeNormalVectors never set: MPAS_DYC_ESTATE naming the input.  Changing
+ * the setting drops the captured steps; uploading a raw tendency does not.  flags = 0: off, and the four
+ * coupled arrays are set to 0.0 (a step that keeps the physics form, for IAU or the device microphysics,
+ * then reads zeros, not the last coupling's values; a host that takes the coupling over uploads its own);
+ * a context that never calls it behaves as before.  On a MPAS_DYC_HOST_ONLY context the setting is kept (for
+ * mpas_dyc_plan_exchanges) and nothing is allocated. */
+#define MPAS_DYC_TODYN_PBL 1          /* config_pbl_scheme /= 'off' */
+#define MPAS_DYC_TODYN_PBL_MYNN 2     /* bl_mynn: rniblten */
+#define MPAS_DYC_TODYN_CU 4           /* config_convection_scheme /= 'off' */
+#define MPAS_DYC_TODYN_CU_KF 8        /* cu_kain_fritsch: rqrcuten, rqscuten */
+#define MPAS_DYC_TODYN_CU_WINDS 16    /* cu_tiedtke / cu_ntiedtke: rucuten, rvcuten */
+#define MPAS_DYC_TODYN_LW 32          /* config_radt_lw_scheme /= 'off' */
+#define MPAS_DYC_TODYN_SW 64          /* config_radt_sw_scheme /= 'off' */
+#define MPAS_DYC_TODYN_RQVDYNTEN 128  /* the step also computes rqvdynten (1629-1643) */
+int mpas_dyc_set_todynamics(mpas_dyc_ctx* ctx, int32_t flags, int32_t index_qc, int32_t index_qr,
+                            int32_t index_qi, int32_t index_qs, int32_t index_ni);
+/* The coupling once, eager and on its own, on time level 1: for hosts that want the coupled arrays, and
+ * for tests.  MPAS_DYC_ESTATE if off, between mpas_dyc_timestep and mpas_dyc_finish_step, or on a
+ * MPAS_DYC_HOST_ONLY context.  Asynchronous on the compute stream (synchronous only while
+ * mpas_dyc_set_profile is on, which times it: mpas_dyc_get_profile out[12]).  Collective across ranks
+ * when a wind flag is on (the halo exchange). */
+int mpas_dyc_physics_get_tend(mpas_dyc_ctx* ctx);
 /* The isobaric output diagnostics and mslp of the reference's `diagnostics` stream
  * (diagnostics/isobaric_diagnostics.F, Registry_isobaric.xml), on the device (isobaric.hip), so a run
  * that writes them need not copy ten 3-D fields to the host at output time.  One bit per group, because
@@ -727,7 +794,8 @@ double mpas_dyc_acoustic_bytes(const mpas_dyc_ctx* ctx);
  * out[9] = the same for the last mpas_dyc_pv_diagnostics called with the profile on (its read-backs
  * included); out[10] = the sweeps of the last mpas_dyc_pv_diagnostics' fill that changed something, the
  * most over the blocks.
- * out[11] = milliseconds of the last mpas_dyc_convective_diagnostics called with the profile on. */
+ * out[11] = milliseconds of the last mpas_dyc_convective_diagnostics called with the profile on.
+ * out[12] = the same for the last mpas_dyc_physics_get_tend called with the profile on. */
 int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on);
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n);
 /* The plan key of the exchange whose RCCL group was enqueued last ("warm_rccl <key>" while the

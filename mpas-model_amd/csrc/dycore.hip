@@ -32,6 +32,7 @@
 #include "lbc.hip"
 #include "model_init.hip"
 #include "iau.hip"
+#include "todynamics.hip"
 #include "convdiag.hip"
 #include "kessler.hip"
 #include "isobaric.hip"
@@ -49,7 +50,7 @@ enum Target { T_NONE, T_CELL, T_EDGE, T_VERTEX, T_SMALL };  // int index semanti
 // coefficients read (mpas_dyc_model_init, mpas_dyc_init_reconstruct).  The others belong to a step hook
 // (physics_host.hip) and are allocated together, zeroed, by alloc_group: when the hook is switched on,
 // or at the first set_field of one of them.
-enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP, G_ISOBARIC, G_PV, G_CONVCOMPUTE };
+enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP, G_ISOBARIC, G_PV, G_CONVCOMPUTE, G_TODYN };
 // all_blocks: a first set_field completes the group on every block (false: on that block only).
 // hidden: mpas_dyc_block_field_bytes reports 0 until the field is allocated -- the fields are held
 // only by a context that asked for them.
@@ -62,6 +63,7 @@ constexpr struct { bool all_blocks, hidden; } GROUPS[] = {
     {true, true},    // G_ISOBARIC: the isobaric diagnostics' outputs, level tables and diag.relhum
     {true, true},    // G_PV: the PV diagnostics' outputs and the three mesh vector arrays they read
     {true, true},    // G_CONVCOMPUTE: cape, cin, the helicities and the surface / 1 km / 6 km fields
+    {true, true},    // G_TODYN: physics_get_tend's raw tendencies, edge projections, tend_u_phys, mesh.east / north
 };
 
 struct Field {
@@ -117,6 +119,7 @@ struct Block {
   bool kite_set = false;               // mesh.kiteAreasOnVertex has been set (the isobaric vorticity reads it)
   int* iso_fail = nullptr;             // compute_slp's failure word of the block (isobaric.hip), on the device
   PvBlock pv;                          // the PV diagnostics' derived table and fill buffers (pv.hip)
+  int todyn_set = 0;                   // TODYN_SET_*: mesh.east / north have been set (todynamics.hip)
   // maxEdges / maxEdges2 as the host declared them (the mesh file's dimensions; Fortran images and
   // h_eoc use these strides).  d.maxEdges / d.maxEdges2 are the strides the kernels index with:
   // max(nEdgesOnCell) and the edgesOnEdge slots the kernels need after pack_mesh
@@ -313,6 +316,7 @@ struct mpas_dyc_ctx {
   ConvState conv;                       // cape, cin, helicity, surface fields (mpas_dyc_set_convective; convcompute.hip)
   ConvDiagState convdiag;               // the convective running maxima (mpas_dyc_set_diag_update; convdiag.hip)
   MicropState microp;                   // the device microphysics (mpas_dyc_set_microphysics; kessler.hip)
+  TodynState todyn;                     // physics_get_tend (mpas_dyc_set_todynamics; todynamics.hip)
   int64_t graph_captures = 0;           // steps captured so far (mpas_dyc_get_profile out[5])
   bool tail_pending = false;            // MPAS_DYC_PHYSICS_MICROPHYSICS: a step ran, mpas_dyc_finish_step not yet
   // exchange profile (mpas_dyc_set_profile): eager steps with HIP events around the exposed part of
@@ -593,6 +597,15 @@ void build_registry(Block& c) {
   // srh_0_3km, uzonal / umeridional _surface / _1km / _6km, temperature_surface, dewpoint_surface, each
   // (nCells + 1); allocated, zeroed, at the first set_field of one of them or at mpas_dyc_set_convective
   for (const char* n : CONV_FIELDS) add(c, "diag", n, L_CELL, 1).group = G_CONVCOMPUTE;
+  // physics_get_tend on the device (todynamics.hip): the raw tendencies of the PBL, convection and radiation
+  // schemes (Registry.xml tend_physics, (K, nCells + 1) each), the edge projections of the wind tendencies
+  // and diag.tend_u_phys ((K, nEdges + 1)), and init_dirs_forphys' mesh.east / north (3, nCells + 1), which
+  // the host sets; allocated, zeroed, at the first set_field of one of them or at mpas_dyc_set_todynamics
+  // with non-zero flags.  No buffer rotation touches them: their device pointers never change.
+  for (const char* n : TODYN_CELL_FIELDS) add(c, "tend_physics", n, L_CELL, K).group = G_TODYN;
+  for (const char* n : {"rublten_Edge", "rucuten_Edge"}) add(c, "tend_physics", n, L_EDGE, K).group = G_TODYN;
+  add(c, "diag", "tend_u_phys", L_EDGE, K).group = G_TODYN;
+  for (const char* n : {"east", "north"}) add(c, "mesh", n, L_CELL, 3).group = G_TODYN;
   // the maxEdges- and maxEdges2-strided mesh arrays (pack_mesh)
   for (const char* n : {"edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "coeffs_reconstruct",
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
@@ -618,6 +631,8 @@ void pv_touch(Block& b, const Field& f) {
   if (f.name == "cellTangentPlane") b.pv.set |= PV_SET_TANGENT;
   if (f.name == "localVerticalUnitVectors") b.pv.set |= PV_SET_VERTICAL;
   if (f.name == "edgeNormalVectors") b.pv.set |= PV_SET_NORMALS;
+  if (f.name == "east") b.todyn_set |= TODYN_SET_EAST;
+  if (f.name == "north") b.todyn_set |= TODYN_SET_NORTH;
 }
 
 Field* find(Block& b, const char* pool, const char* name) {
@@ -643,17 +658,20 @@ T* P(mpas_dyc_ctx* c, Block& b, const char* pool, const char* name, int tl = 1) 
   return (T*)(f->packed ? f->packed : f->buf[slot_of(c, *f, tl)]);
 }
 
-// DO_PHYSICS coupling of the step: the host's flag, or implied by the incremental analysis update
-// or by the device microphysics
+// DO_PHYSICS coupling of the step: the host's flag, or implied by the incremental analysis update,
+// by the device microphysics or by the device's physics_get_tend
 bool physics_tendencies(const mpas_dyc_ctx* c) {
-  return (c->physics & MPAS_DYC_PHYSICS_TENDENCIES) || c->iau.on || c->microp.scheme;
+  return (c->physics & MPAS_DYC_PHYSICS_TENDENCIES) || c->iau.on || c->microp.scheme || c->todyn.flags;
 }
+// tend_physics.tend_*_physics and tend.scalars_tend hold a step's coupled tendencies: the host's
+// (mpas_dyc_set_physics) or the device's physics_get_tend's (mpas_dyc_set_todynamics)
+bool coupled_tendencies(const mpas_dyc_ctx* c) { return (c->physics & MPAS_DYC_PHYSICS_TENDENCIES) || c->todyn.flags; }
 // the step being enqueued applies the IAU forcing (mpas_atm_iau.F:118)
 bool iau_active(const mpas_dyc_ctx* c) { return c->iau.on && c->iau.wgt > 1.0e-12; }
 // Ptrs::tend_*_physics are the library's sums (scratch.iau_*): in a forced step, and in every step of
 // a host that supplies no physics tendencies (then they hold the zeros it would have supplied)
 bool iau_sums(const mpas_dyc_ctx* c) {
-  return c->iau.on && (iau_active(c) || !(c->physics & MPAS_DYC_PHYSICS_TENDENCIES));
+  return c->iau.on && (iau_active(c) || !coupled_tendencies(c));
 }
 
 Ptrs make_ptrs(mpas_dyc_ctx* c, Block& b) {
@@ -1969,6 +1987,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
   EACH(if (pair_layout(d)) LAUNCH_PE((k_moist_edges_p<false>), (k_moist_edges_p<true>), d.nEdges, d, p);
        else LAUNCH(k_moist_edges, d.nEdges, d, p));
   // physics tendencies are zero without DO_PHYSICS (450-457): scratch arrays stay zero.
+  if (ctx->todyn.flags) CHK(todyn_step(ctx, P));                  // 424-449: physics_get_tend
   if (iau_active(ctx)) CHK(iau_add_tend(ctx, P));                 // 459-469: atm_add_tend_anal_incr
 
   // Deferred exchanges.  With split-phase exchanges, the exchange after the diagnostics
@@ -2286,7 +2305,7 @@ int srk3(mpas_dyc_ctx* ctx, double dt) {
   if (physics_tendencies(ctx)) {                                   // DO_PHYSICS block, 1610-1648
     // rqvdynten (1629-1643) for cu_grell_freitas / cu_tiedtke / cu_ntiedtke, from the scalars before
     // the clip; the microphysics call itself (1650-1660) belongs to the host, after this step
-    if (ctx->physics & MPAS_DYC_PHYSICS_RQVDYNTEN)
+    if ((ctx->physics & MPAS_DYC_PHYSICS_RQVDYNTEN) || (ctx->todyn.flags & TODYN_RQVDYNTEN))
       EACH(LAUNCH(k_physics_rqvdynten, d.nCells + 1, d, p, ctx->index_qv, cf.monotonic, dt));
     for (auto& b : ctx->blk) {
       const int64_t n = (int64_t)b.d.ns * (b.d.nCells + 1) * b.d.K;
@@ -3516,12 +3535,13 @@ int mpas_dyc_timestep(mpas_dyc_ctx* ctx, double dt, int32_t itimestep) {
   if (!ctx || !(dt > 0.0)) return MPAS_DYC_EINVAL;
   if (ctx->host_only) return MPAS_DYC_ESTATE;
   HIPCHK(hipSetDevice(ctx->device));
+  if (ctx->todyn.flags) CHK(todyn_check_inputs(ctx, "mpas_dyc_timestep"));
   // atm_iau_coef of this step (mpas_atm_iau.F:22-78): which of the two captured steps runs, never a
   // reason to capture again (the weight is the same for every forced step)
   CHK(mpas_dyc_iau_weight(ctx, dt, itimestep, &ctx->iau.wgt));
   if (iau_active(ctx)) {
     ctx->iau.stale = true;
-  } else if (ctx->iau.on && ctx->iau.stale && !(ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES)) {
+  } else if (ctx->iau.on && ctx->iau.stale && !coupled_tendencies(ctx)) {
     // an unforced step of a host that supplies no tendencies reads the library's arrays: zeros
     for (auto& b : ctx->blk)
       for (const char* n : {"scratch.iau_ru", "scratch.iau_rtheta", "scratch.iau_rho", "tend.scalars_tend"}) {
@@ -3616,7 +3636,7 @@ int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on) {
 
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n) {
   if (!ctx || !out || n < 1) return MPAS_DYC_EINVAL;
-  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : i == 8 ? ctx->iso.ms : i == 9 ? ctx->pv.ms : i == 10 ? (double)ctx->pv.sweeps : i == 11 ? ctx->conv.ms : 0.0;
+  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : i == 8 ? ctx->iso.ms : i == 9 ? ctx->pv.ms : i == 10 ? (double)ctx->pv.sweeps : i == 11 ? ctx->conv.ms : i == 12 ? ctx->todyn.ms : 0.0;
   return MPAS_DYC_OK;
 }
 

@@ -1,14 +1,15 @@
-// Host side of the step's physics hooks: the incremental analysis update (kernels: iau.hip), the
+// Host side of the step's physics hooks: the incremental analysis update (kernels: iau.hip), the coupling
+// of the physics tendencies (physics_get_tend: todynamics.hip), the
 // convective running maxima (convdiag.hip), the device microphysics (kessler.hip), the isobaric output
 // diagnostics (isobaric.hip), the PV diagnostics (pv.hip) and the output-time convective diagnostics
 // (convcompute.hip; the last three are not part of the step, but hooks of the same shape).  Per hook: what
 // enqueues its kernels, and its entry points of include/mpas_dycore.h.  A hook's state struct
-// (mpas_dyc_ctx::iau / convdiag / microp / iso / pv / conv, Block::cv / pv) stands next to its kernels' argument struct; its
+// (mpas_dyc_ctx::iau / todyn / convdiag / microp / iso / pv / conv, Block::cv / pv) stands next to its kernels' argument struct; its
 // fields are a Group of the registry (dycore.hip build_registry), allocated by alloc_group.
 //
 // Included by dycore.hip inside its namespace, before srk3: after the structs (Field, Block,
 // mpas_dyc_ctx), HIPCHK / CHK, find, P, field_bytes, physics_tendencies, drop_graphs, require_device,
-// alloc_group, group_ready, timed_on_stream, iso_field_name and compute_bnd.  The file closes that namespace for its
+// alloc_group, group_ready, timed_on_stream, iso_field_name, compute_bnd, exchange and block_ptrs.  The file closes that namespace for its
 // extern "C" entry points and opens it again at its end.
 
 // ---- incremental analysis update ----
@@ -17,7 +18,7 @@
 // host's tend_physics arrays themselves (nullptr, read as 0.0, when the host supplies none).
 int iau_add_tend(mpas_dyc_ctx* ctx, const std::vector<Ptrs>& P) {
   if (ctx->planning) return MPAS_DYC_OK;
-  const bool host_phys = (ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES) != 0;
+  const bool host_phys = coupled_tendencies(ctx);  // the host's, or the device's physics_get_tend's
   for (size_t ib = 0; ib < ctx->blk.size(); ++ib) {
     Block& b = ctx->blk[ib];
     const Dims& d = b.d;
@@ -414,9 +415,174 @@ int conv_enqueue(mpas_dyc_ctx* ctx, int tl) {
   return MPAS_DYC_OK;
 }
 
+// ---- physics_get_tend ----
+// the wind tendencies are projected to the edges: the PBL's, a Tiedtke scheme's
+bool todyn_winds(int flags) { return (flags & (TODYN_PBL | TODYN_CU_WINDS)) != 0; }
+
+// a needed mesh input of block b that was never set, or nullptr
+const char* todyn_missing_input(const mpas_dyc_ctx* ctx, const Block& b) {
+  if (!todyn_winds(ctx->todyn.flags)) return nullptr;
+  if (!(b.todyn_set & TODYN_SET_EAST)) return "mesh.east";
+  if (!(b.todyn_set & TODYN_SET_NORTH)) return "mesh.north";
+  if (!(b.pv.set & PV_SET_NORMALS)) return "mesh.edgeNormalVectors";
+  return nullptr;
+}
+int todyn_check_inputs(mpas_dyc_ctx* ctx, const char* entry) {
+  for (const auto& b : ctx->blk)
+    if (const char* missing = todyn_missing_input(ctx, b)) {
+      ctx->err = std::string(entry) + ": physics_get_tend needs " + missing + ", which was never set";
+      return MPAS_DYC_ESTATE;
+    }
+  return MPAS_DYC_OK;
+}
+
+// physics_get_tend of every block from the fields of time level 1 that P names (rho_zz of time level 2 has
+// the same bits after atm_rk_integration_setup, :369): the halo of the raw wind tendencies (:474-492, only
+// when a wind flag is on), then the edge and the cell kernel.  The results go to tend_physics.tend_*_physics
+// and tend.scalars_tend themselves, whatever P's tend_*_physics point at (the IAU sums read them).
+int todyn_step(mpas_dyc_ctx* ctx, const std::vector<Ptrs>& P) {
+  const TodynState& t = ctx->todyn;
+  const int fl = t.flags;
+  if (todyn_winds(fl)) {
+    std::vector<XField> fs;
+    if (fl & TODYN_PBL) fs.insert(fs.end(), {{"tend_physics", "rublten", 0, ALL_LAYERS}, {"tend_physics", "rvblten", 0, ALL_LAYERS}});
+    if (fl & TODYN_CU_WINDS) fs.insert(fs.end(), {{"tend_physics", "rucuten", 0, ALL_LAYERS}, {"tend_physics", "rvcuten", 0, ALL_LAYERS}});
+    CHK((exchange)(ctx, fs));
+  }
+  if (ctx->planning) return MPAS_DYC_OK;
+  for (size_t ib = 0; ib < ctx->blk.size(); ++ib) {
+    Block& b = ctx->blk[ib];
+    const Dims& d = b.d;
+    const Ptrs& p = P[ib];
+    auto raw = [&](const char* n) { return ::P<const double>(ctx, b, "tend_physics", n); };
+    TodynEdges e{};
+    e.nEdges = d.nEdges, e.nEdgesSolve = d.nEdgesSolve, e.nCells = d.nCells, e.K = d.K;
+    e.group = d.K > 32 ? 64 : d.K > 16 ? 32 : 16;
+    e.pbl = (fl & TODYN_PBL) != 0, e.cu = (fl & TODYN_CU_WINDS) != 0;
+    e.cellsOnEdge = p.cellsOnEdge;
+    e.east = ::P<const double>(ctx, b, "mesh", "east"), e.north = ::P<const double>(ctx, b, "mesh", "north");
+    e.edgeNormalVectors = ::P<const double>(ctx, b, "mesh", "edgeNormalVectors");
+    e.rublten = raw("rublten"), e.rvblten = raw("rvblten"), e.rucuten = raw("rucuten"), e.rvcuten = raw("rvcuten");
+    e.rho_edge = p.rho_edge;
+    e.rublten_Edge = ::P<double>(ctx, b, "tend_physics", "rublten_Edge");
+    e.rucuten_Edge = ::P<double>(ctx, b, "tend_physics", "rucuten_Edge");
+    e.tend_u_phys = ::P<double>(ctx, b, "diag", "tend_u_phys");
+    e.tend_ru_physics = ::P<double>(ctx, b, "tend_physics", "tend_ru_physics");
+    const int64_t per_block = TODYN_THREADS / e.group;
+    auto grid = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(n, TODYN_MAX_BLOCKS))); };
+    hipLaunchKernelGGL(k_todyn_edges, grid(((int64_t)d.nEdges + 1 + per_block - 1) / per_block), dim3(TODYN_THREADS), 0,
+                       ctx->stream, e);
+
+    TodynCells a{};
+    a.n = a.plane = (int64_t)(d.nCells + 1) * d.K;
+    a.n_solve = (int64_t)d.nCellsSolve * d.K;
+    a.ns = d.ns, a.index_qv = ctx->index_qv;
+    auto th = [&](const char* n) { a.th[a.nth++] = raw(n); };
+    auto term = [&](const char* n, int plane) {  // an absent scalar's term is skipped
+      if (plane < 0) return;
+      a.term[a.nterm] = raw(n);
+      a.term_plane[a.nterm++] = plane;
+    };
+    if (fl & TODYN_PBL) {                          // :343-364
+      th("rthblten");
+      term("rqvblten", ctx->index_qv), term("rqcblten", t.iqc), term("rqiblten", t.iqi);
+      if (fl & TODYN_PBL_MYNN) term("rniblten", t.ini);
+    }
+    if (fl & TODYN_CU) {                           // :368-387
+      th("rthcuten");
+      term("rqvcuten", ctx->index_qv), term("rqccuten", t.iqc), term("rqicuten", t.iqi);
+      if (fl & TODYN_CU_KF) term("rqrcuten", t.iqr), term("rqscuten", t.iqs);
+    }
+    if (fl & TODYN_LW) th("rthratenlw");           // :407-413
+    if (fl & TODYN_SW) th("rthratensw");           // :416-422
+    a.mass = p.rho_zz1, a.theta_m = p.theta_m1;
+    a.qv = p.scalars1 + (int64_t)ctx->index_qv * a.plane;
+    a.tend_rtheta = ::P<double>(ctx, b, "tend_physics", "tend_rtheta_physics");
+    a.tend_rho = ::P<double>(ctx, b, "tend_physics", "tend_rho_physics");
+    a.scalars_tend = ::P<double>(ctx, b, "tend", "scalars_tend");
+    auto cgrid = [](int64_t n) {
+      return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + TODYN_THREADS - 1) / TODYN_THREADS, TODYN_MAX_BLOCKS)));
+    };
+    if (a.n & 1) hipLaunchKernelGGL(k_todyn_cells<false>, cgrid(a.n), dim3(TODYN_THREADS), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(k_todyn_cells<true>, cgrid(a.n / 2), dim3(TODYN_THREADS), 0, ctx->stream, a);
+  }
+  return MPAS_DYC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mpas_dyc_set_todynamics(mpas_dyc_ctx* ctx, int32_t flags, int32_t index_qc, int32_t index_qr, int32_t index_qi,
+                            int32_t index_qs, int32_t index_ni) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  const char* bad = nullptr;
+  if (flags & ~TODYN_ALL) bad = "unknown flag bits";
+  else if ((flags & TODYN_PBL_MYNN) && !(flags & TODYN_PBL)) bad = "MPAS_DYC_TODYN_PBL_MYNN without MPAS_DYC_TODYN_PBL";
+  else if ((flags & (TODYN_CU_KF | TODYN_CU_WINDS)) && !(flags & TODYN_CU))
+    bad = "MPAS_DYC_TODYN_CU_KF / _CU_WINDS without MPAS_DYC_TODYN_CU";
+  else if ((flags & TODYN_CU_KF) && (flags & TODYN_CU_WINDS)) bad = "MPAS_DYC_TODYN_CU_KF together with MPAS_DYC_TODYN_CU_WINDS";
+  const int ns = ctx->blk.empty() ? 0 : ctx->blk[0].d.ns;
+  if (!bad && flags)
+    for (int32_t i : {index_qc, index_qr, index_qi, index_qs, index_ni})
+      if (i > ns || (i > 0 && i - 1 == ctx->index_qv)) bad = "an index is above num_scalars or equal to index_qv";
+  if (bad) {
+    ctx->err = std::string("mpas_dyc_set_todynamics: ") + bad;
+    return MPAS_DYC_EINVAL;
+  }
+  if (flags && (ctx->physics & MPAS_DYC_PHYSICS_TENDENCIES)) {
+    ctx->err = "mpas_dyc_set_todynamics with MPAS_DYC_PHYSICS_TENDENCIES (the host's coupled tendencies) set";
+    return MPAS_DYC_ESTATE;
+  }
+  if (!ctx->host_only) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (flags && !group_ready(ctx, G_TODYN)) CHK(alloc_group(ctx, G_TODYN));
+  }
+  const bool replan = (flags & (TODYN_PBL | TODYN_CU_WINDS)) != (ctx->todyn.flags & (TODYN_PBL | TODYN_CU_WINDS));
+  if (!flags && ctx->todyn.flags && !ctx->host_only)
+    // off: the coupled arrays go back to the zeros of a context that never coupled, so a step that keeps the
+    // physics form (IAU, the device microphysics) does not go on applying the last coupling's values
+    for (auto& b : ctx->blk)
+      for (const char* n : {"tend_physics.tend_ru_physics", "tend_physics.tend_rtheta_physics",
+                            "tend_physics.tend_rho_physics", "tend.scalars_tend"}) {
+        Field& f = b.fields[b.by_name[n]];
+        HIPCHK(hipMemsetAsync(f.buf[0], 0, field_bytes(b, f), ctx->stream));
+      }
+  ctx->todyn.flags = flags;
+  if (flags) {
+    ctx->todyn.iqc = index_qc - 1, ctx->todyn.iqr = index_qr - 1, ctx->todyn.iqi = index_qi - 1;
+    ctx->todyn.iqs = index_qs - 1, ctx->todyn.ini = index_ni - 1;
+    for (int* i : {&ctx->todyn.iqc, &ctx->todyn.iqr, &ctx->todyn.iqi, &ctx->todyn.iqs, &ctx->todyn.ini})
+      if (*i < 0) *i = -1;
+  }
+  for (auto& b : ctx->blk) b.d.physics = physics_tendencies(ctx) ? 1 : 0;
+  ctx->iau.stale = ctx->iau.on != 0;
+  // captured steps bake the flags and the indices in; the wind flags decide an exchange point of the step
+  if (replan) invalidate_plans(ctx);
+  else if (!ctx->host_only) drop_graphs(ctx);
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_physics_get_tend(mpas_dyc_ctx* ctx) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  CHK(require_device(ctx));
+  if (ctx->tail_pending) {
+    ctx->err = "mpas_dyc_physics_get_tend between mpas_dyc_timestep and mpas_dyc_finish_step";
+    return MPAS_DYC_ESTATE;
+  }
+  if (!ctx->todyn.flags) {
+    ctx->err = "mpas_dyc_physics_get_tend: no scheme set (mpas_dyc_set_todynamics)";
+    return MPAS_DYC_ESTATE;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  CHK(todyn_check_inputs(ctx, "mpas_dyc_physics_get_tend"));
+  return timed_on_stream(ctx, ctx->todyn.ms, [&]() -> int {
+    CHK(todyn_step(ctx, block_ptrs(ctx)));
+    HIPCHK(hipGetLastError());
+    return MPAS_DYC_OK;
+  });
+}
 
 int mpas_dyc_set_convective(mpas_dyc_ctx* ctx, int32_t flags) {
   if (!ctx) return MPAS_DYC_EINVAL;
@@ -519,18 +685,23 @@ int mpas_dyc_isobaric_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level) {
 int mpas_dyc_set_physics(mpas_dyc_ctx* ctx, int32_t flags) {
   if (!ctx || (flags & ~(MPAS_DYC_PHYSICS_TENDENCIES | MPAS_DYC_PHYSICS_RQVDYNTEN | MPAS_DYC_PHYSICS_MICROPHYSICS)))
     return MPAS_DYC_EINVAL;
-  if (ctx->host_only) return MPAS_DYC_ESTATE;
   if ((flags & MPAS_DYC_PHYSICS_RQVDYNTEN) && !(flags & MPAS_DYC_PHYSICS_TENDENCIES)) return MPAS_DYC_EINVAL;
   if ((flags & MPAS_DYC_PHYSICS_MICROPHYSICS) && ctx->microp.scheme) {
     ctx->err = "MPAS_DYC_PHYSICS_MICROPHYSICS (the host's microphysics) with mpas_dyc_set_microphysics on";
     return MPAS_DYC_ESTATE;
   }
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if ((flags & MPAS_DYC_PHYSICS_TENDENCIES) && ctx->todyn.flags) {
+    ctx->err = "MPAS_DYC_PHYSICS_TENDENCIES (the host's coupled tendencies) with mpas_dyc_set_todynamics on";
+    return MPAS_DYC_ESTATE;
+  }
+  if (!ctx->host_only) {  // a planner's context keeps the flags alone
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
   ctx->physics = flags;
   for (auto& b : ctx->blk) b.d.physics = physics_tendencies(ctx) ? 1 : 0;
   ctx->iau.stale = ctx->iau.on != 0;
-  drop_graphs(ctx);  // captured steps bake the flags in
+  if (!ctx->host_only) drop_graphs(ctx);  // captured steps bake the flags in
   return MPAS_DYC_OK;
 }
 

@@ -32,6 +32,7 @@ EXPORTS = (
     "mpas_dyc_diag_update", "mpas_dyc_diag_reset", "mpas_dyc_folded_passes", "mpas_dyc_set_microphysics",
     "mpas_dyc_microphysics", "mpas_dyc_set_isobaric", "mpas_dyc_isobaric_diagnostics", "mpas_dyc_set_pv",
     "mpas_dyc_pv_diagnostics", "mpas_dyc_set_convective", "mpas_dyc_convective_diagnostics",
+    "mpas_dyc_set_todynamics", "mpas_dyc_physics_get_tend",
 )
 HOST_ONLY = -2  # MPAS_DYC_HOST_ONLY: planner-only context
 PRINT_GLOBAL_MINMAX_VEL, PRINT_DETAILED_MINMAX_VEL, PRINT_GLOBAL_MINMAX_SCA = 1, 2, 4
@@ -48,6 +49,10 @@ ISO_ALL = 4095
  CONV_UZONAL_6KM, CONV_UMERIDIONAL_SURFACE, CONV_UMERIDIONAL_1KM, CONV_UMERIDIONAL_6KM, CONV_TEMPERATURE_SURFACE,
  CONV_DEWPOINT_SURFACE) = (1 << i for i in range(14))
 CONV_ALL = 16383
+# MPAS_DYC_TODYN_*: the schemes of mpas_dyc_set_todynamics (physics_get_tend on the device)
+(TODYN_PBL, TODYN_PBL_MYNN, TODYN_CU, TODYN_CU_KF, TODYN_CU_WINDS, TODYN_LW, TODYN_SW,
+ TODYN_RQVDYNTEN) = (1 << i for i in range(8))
+TODYN_ALL = 255
 CELL, EDGE, VERTEX = 0, 1, 2
 SEND, RECV = 0, 1
 
@@ -156,6 +161,8 @@ def load() -> C.CDLL:
     lib.mpas_dyc_pv_diagnostics.argtypes = [vp, i32]
     lib.mpas_dyc_set_convective.argtypes = [vp, i32]
     lib.mpas_dyc_convective_diagnostics.argtypes = [vp, i32]
+    lib.mpas_dyc_set_todynamics.argtypes = [vp, i32, i32, i32, i32, i32, i32]
+    lib.mpas_dyc_physics_get_tend.argtypes = [vp]
     lib.mpas_dyc_time_acoustic_step.argtypes = [vp, dbl, i32, i32, C.POINTER(dbl), C.POINTER(dbl)]
     lib.mpas_dyc_use_graph.argtypes = [vp, i32]
     lib.mpas_dyc_acoustic_bytes.argtypes = [vp]

@@ -309,6 +309,30 @@ def physics_forcing(case: dict, scale: float = 1.0) -> dict:
     return f
 
 
+def raw_physics_forcing(case: dict, scale: float = 1.0) -> dict:
+    """Smooth raw tendencies of the PBL, convection and radiation schemes (the tend_physics pool that
+    physics_get_tend couples: rublten ... rthratensw, fields.TODYN_RAW), element-major (nCells, K).  They are
+    physics_forcing's coupled tendencies split between the schemes and divided by the case's rho_zz, so
+    what physics_get_tend makes of them on the initial state has physics_forcing's size -- its drying aloft
+    included -- and both signs; every field has its own pattern, so a swapped pair shows."""
+    K = case["nVertLevels"]
+    kk = (np.arange(K) + 0.5) / K
+    latc, lonc = case["latCell"][:, None], case["lonCell"][:, None]
+    rho = np.asarray(case["rho"], dtype=np.float64) / np.asarray(case["zz"], dtype=np.float64)
+    wave = lambda i: np.cos((i + 1) * latc) * np.sin(lonc + i) * (1 - kk) ** (i % 3 + 1)  # noqa: E731
+    th = 3e-4 * np.cos(latc) ** 2 * np.exp(-3 * kk)
+    f = dict(
+        rublten=2e-4 * np.cos(latc) * np.sin(2 * lonc) * (1 - kk), rvblten=1.5e-4 * np.sin(2 * latc) * np.cos(lonc) * (1 - kk),
+        rucuten=1e-4 * np.cos(latc) * np.cos(3 * lonc + 0.4) * kk * (1 - kk), rvcuten=8e-5 * np.sin(latc) * np.sin(lonc - 0.3) * kk,
+        rthblten=0.4 * th * (1 + 0.5 * np.sin(lonc)), rthcuten=0.3 * th * (1 + 0.5 * np.cos(2 * lonc)) * 4 * kk * (1 - kk),
+        rthratenlw=-0.2 * th * (1 + 0.3 * np.sin(latc)), rthratensw=0.3 * th * np.maximum(np.cos(lonc), 0.0),
+        rqvblten=0.6e-7 * wave(0) - 5e-7 * kk ** 2, rqvcuten=0.4e-7 * wave(1),
+        rqcblten=1e-8 * wave(2), rqccuten=2e-8 * wave(3), rqiblten=0.5e-8 * wave(4), rqicuten=1e-8 * wave(5),
+        rqrcuten=1.5e-8 * wave(6), rqscuten=1e-8 * wave(7), rniblten=1e2 * wave(8),
+    )
+    return {n: scale * a / rho for n, a in f.items()}
+
+
 FORECAST_DT = 600.0
 FORECAST_NS = 3
 

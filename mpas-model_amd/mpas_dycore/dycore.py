@@ -116,13 +116,14 @@ def _install_lists(lib, h, blocks, placement, check, positional_rank=None, inclu
 
 def plan_exchanges(blocks: list, placement: dict, rank: int, nranks: int, dt: float, moist_end: int = 1,
                    overlap: bool | None = None, positional: bool = False,
-                   p2p: bool = False) -> tuple[np.ndarray, list[str]]:
+                   p2p: bool = False, todynamics: int = 0) -> tuple[np.ndarray, list[str]]:
     """Dry run of the exchange planner for one rank, on the host (no GPU): the RCCL messages
     this rank posts over model init and one step on each time-level parity, and the plan key of
     every exchange call in issue order (mpas_dyc_plan_exchanges).  Messages are a structured array
     with fields point, direction (_lib.SEND / _lib.RECV), block, peer_rank, peer_block, count.
     p2p: as planned for the one-sided transfer (mpas_dyc_set_p2p; the same messages, every exchange
-    blocking)."""
+    blocking).  todynamics: the MPAS_DYC_TODYN_* mask of mpas_dyc_set_todynamics (its wind flags add the halo
+    exchange of the raw wind tendencies to every step)."""
     lib = _lib.load()
     cases = [b.case for b in blocks]
     dims = _make_dims(cases, [b.solve for b in blocks], moist_end)
@@ -141,6 +142,8 @@ def plan_exchanges(blocks: list, placement: dict, rank: int, nranks: int, dt: fl
         check(lib.mpas_dyc_set_overlap(h, -1 if overlap is None else int(bool(overlap))), "set_overlap")
         if p2p:
             check(lib.mpas_dyc_set_p2p(h, 1), "set_p2p")
+        if todynamics:
+            check(lib.mpas_dyc_set_todynamics(h, int(todynamics), 0, 0, 0, 0, 0), "set_todynamics")
         nm, kl = C.c_int64(), C.c_int64()
         lib.mpas_dyc_plan_exchanges(h, int(nranks), int(rank), float(dt), None, 0, C.byref(nm), None, 0,
                                     C.byref(kl))
@@ -183,6 +186,7 @@ class Dycore:
         if rc != 0 or not h.value:
             raise DycoreError(f"mpas_dyc_create_blocks failed ({rc})")
         self.h = h
+        self._mesh_set = set()  # (block, name) of the mesh fields uploaded so far
         if model_init not in ("host", "device", "device_cr"):
             raise ValueError("model_init: 'host' (the case's precomputed arrays), 'device' (mpas_dyc_model_init with "
                              "the C library's x**0.25 / sin from the host) or 'device_cr' (correctly rounded on the device)")
@@ -269,6 +273,8 @@ class Dycore:
 
     def set_raw(self, pool: str, name: str, fortran_image: np.ndarray, time_level: int = 1, block: int = 0):
         a = np.ascontiguousarray(fortran_image)
+        if pool == "mesh":
+            self._mesh_set.add((block, name))
         self._check(self.lib.mpas_dyc_set_block_field(self.h, block, pool.encode(), name.encode(), time_level,
                                                       a.ctypes.data_as(C.c_void_p), a.nbytes),
                     f"set {pool}.{name}")
@@ -332,7 +338,7 @@ class Dycore:
                 for name, a in lm.items():
                     self.set_raw("mesh", name, to_fortran({**case, name: a}, name), block=block)
         for name in case:
-            if name in _SKIP or name in F.IAU_FIELD or (device_init and name in MODEL_INIT_OUT) or (device_rec and name == "coeffs_reconstruct"):
+            if name in _SKIP or name in F.IAU_FIELD or name in F.TODYN_RAW or name in F.TODYN_EDGE or (device_init and name in MODEL_INIT_OUT) or (device_rec and name == "coeffs_reconstruct"):
                 continue
             if name in F.LOCATION or name in F.VERTICAL_1D:
                 if name in F.VERTICAL_1D:
@@ -348,6 +354,9 @@ class Dycore:
         for name, field in F.IAU_FIELD.items():  # the analysis increments, when the case carries them
             if name in case:
                 self.set_raw("tend_iau", field, to_fortran(case, name), block=block)
+        for name in F.TODYN_RAW:  # the raw physics tendencies, when the case carries them
+            if name in case:
+                self.set_raw("tend_physics", name, to_fortran(case, name), block=block)
 
     # -------------------------------------------------------- operators
     def init_diagnostics(self, dt: float):
@@ -620,6 +629,53 @@ class Dycore:
         out = (C.c_double * 12)()
         self._check(self.lib.mpas_dyc_get_profile(self.h, out, 12), "get_profile")
         return float(out[11])
+
+    def set_todynamics(self, pbl: str | None = None, convection: str | None = None, lw=False, sw=False,
+                       rqvdynten: bool = False, index_qc: int = 0, index_qr: int = 0, index_qi: int = 0,
+                       index_qs: int = 0, index_ni: int = 0, flags: int | None = None):
+        """physics_get_tend on the device (mpas_dyc_set_todynamics): every atm_timestep couples the raw
+        tendencies of the ``tend_physics`` pool (``fields.TODYN_RAW``: rublten ... rthratensw, set through
+        set / set_raw or written through the fields' device pointers, zero until then) into
+        tend_ru_physics / tend_rtheta_physics / tend_rho_physics / scalars_tend, so the host uploads a raw
+        tendency only when a scheme produced a new one.  ``pbl`` / ``convection``: config_pbl_scheme /
+        config_convection_scheme by the reference's names (None or "off": none); ``lw`` / ``sw``:
+        config_radt_lw_scheme / config_radt_sw_scheme is not 'off' (a bool, or the scheme's name);
+        ``rqvdynten``: the step also computes tend_physics.rqvdynten.  ``index_q*`` / ``index_ni``: the
+        1-based scalar indices, 0 for a scalar the run does not carry (its terms are skipped).  ``flags``:
+        the MPAS_DYC_TODYN_* mask itself instead of the names.  Everything off: the hook is off.  Not together
+        with set_physics(tendencies=True).  The wind tendencies are projected with ``mesh.east`` /
+        ``mesh.north`` (the case's, uploaded by the constructor, or set()) and ``mesh.edgeNormalVectors`` (set(),
+        or the case's, which is uploaded here if the block's has never been set); todynamics.with_vectors adds
+        the three to a case.  Without them a step raises, naming the missing one.  mpas_dycore.todynamics is
+        the numpy restatement."""
+        from . import todynamics as T
+        if flags is None:
+            flags = T.scheme_flags(pbl, convection, lw, sw, rqvdynten)
+        self._check(self.lib.mpas_dyc_set_todynamics(self.h, int(flags), int(index_qc), int(index_qr), int(index_qi),
+                                                     int(index_qs), int(index_ni)), "set_todynamics")
+        if not flags & (T.PBL | T.CU_WINDS):
+            return
+        for ib, c in enumerate(self.cases):  # the constructor leaves the PV diagnostics' mesh vectors to their hooks
+            if "edgeNormalVectors" in c and (ib, "edgeNormalVectors") not in self._mesh_set:
+                self.set_raw("mesh", "edgeNormalVectors", to_fortran(c, "edgeNormalVectors"), block=ib)
+
+    def physics_get_tend(self):
+        """The coupling of set_todynamics once, eagerly and on its own, on time level 1
+        (mpas_dyc_physics_get_tend): for hosts that want the coupled arrays, and for tests.  Asynchronous;
+        collective across ranks when a wind tendency is projected (its halo exchange)."""
+        self._check(self.lib.mpas_dyc_physics_get_tend(self.h), "physics_get_tend")
+
+    def physics_get_tend_ms(self) -> float:
+        """Milliseconds of one physics_get_tend() call between HIP events (mpas_dyc_get_profile out[12]);
+        synchronous."""
+        self._check(self.lib.mpas_dyc_set_profile(self.h, 1), "set_profile")
+        try:
+            self.physics_get_tend()
+        finally:
+            self._check(self.lib.mpas_dyc_set_profile(self.h, 0), "set_profile")
+        out = (C.c_double * 13)()
+        self._check(self.lib.mpas_dyc_get_profile(self.h, out, 13), "get_profile")
+        return float(out[12])
 
     def finish_step(self, dt: float):
         """The end of atm_srk3 after the host's microphysics (1672-1794); a no-op unless

@@ -75,6 +75,16 @@ CONV_OUTPUTS = ("cape", "cin", "lcl", "lfc", "srh_0_1km", "srh_0_3km", "uzonal_s
                 "umeridional_surface", "umeridional_1km", "umeridional_6km", "temperature_surface", "dewpoint_surface")
 LOCATION.update({n: "cell" for n in CONV_OUTPUTS})
 
+# physics_get_tend on the device (mpas_dyc_set_todynamics): the raw tendencies of the PBL, convection and
+# radiation schemes (tend_physics pool, one column per cell), the edge projections of the wind tendencies
+# (tend_physics) and diag.tend_u_phys (one column per edge), and init_dirs_forphys' mesh.east / north
+TODYN_RAW = ("rublten", "rvblten", "rthblten", "rqvblten", "rqcblten", "rqiblten", "rniblten", "rucuten", "rvcuten",
+             "rthcuten", "rqvcuten", "rqccuten", "rqrcuten", "rqicuten", "rqscuten", "rthratenlw", "rthratensw")
+TODYN_EDGE = ("rublten_Edge", "rucuten_Edge", "tend_u_phys")
+TODYN_MESH_INPUTS = ("east", "north")
+LOCATION.update({n: "cell" for n in TODYN_RAW + TODYN_MESH_INPUTS})
+LOCATION.update({n: "edge" for n in TODYN_EDGE})
+
 VERTICAL_1D = ("fzm", "fzp", "rdzw", "rdzu", "u_init", "v_init")
 SCALARS_0D = ("cf1", "cf2", "cf3")
 
