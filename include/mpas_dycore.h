@@ -458,8 +458,8 @@ int mpas_dyc_set_pv(mpas_dyc_ctx* ctx, int32_t on);
  * operand order, no contraction: every output has the reference's bits, with one defined deviation -- at
  * level nVertLevels the reference forms dv_dz from velCellp, a local it never set there (:997), so its
  * ertel_pv(nVertLevels, :) is undefined; this library takes velCellm, as the u line two above it does.
- * The PV budget (calc_pvBudget, depv_dt_*) needs the physics suites' tendencies and stays with the host;
- * floodFill_strato, which the reference never calls, is not provided.
+ * The PV budget (calc_pvBudget, depv_dt_*) is mpas_dyc_pv_budget_diagnostics below; floodFill_strato, which
+ * the reference never calls, is not provided.
  * SYNCHRONOUS: the fill's sweeps run in small batches and the host reads a flag back after each, so the
  * call returns with the outputs complete.  Always eager, never part of the step's captured graph, which
  * stays as it is.  Under mpas_dyc_set_profile its milliseconds are mpas_dyc_get_profile out[9].
@@ -468,6 +468,61 @@ int mpas_dyc_set_pv(mpas_dyc_ctx* ctx, int32_t on);
  * mpas_dyc_finish_step with MPAS_DYC_PHYSICS_MICROPHYSICS; a needed mesh input never set (the three vector
  * arrays, areaCell, kiteAreasOnVertex, cellsOnVertex), with a message that names it. */
 int mpas_dyc_pv_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level);
+/* The Ertel PV budget of the same stream (atm_compute_pvBudget_diagnostics, pv_diagnostics.F:1291-1613), on
+ * the device (pvbudget.hip), so a run that writes a depv_dt_* field need not copy the raw theta tendencies,
+ * tend_u_phys, tend.u_euler / w_euler / theta_euler, rho_edge and the PV diagnostics' inputs to the host at
+ * output time.  The mask: */
+#define MPAS_DYC_PVB_ON 1    /* any depv_dt_* / dtheta_dt_mp will be written */
+#define MPAS_DYC_PVB_LW 2    /* rthratenlw is associated */
+#define MPAS_DYC_PVB_SW 4    /* rthratensw */
+#define MPAS_DYC_PVB_BL 8    /* rthblten  */
+#define MPAS_DYC_PVB_CU 16   /* rthcuten  */
+/* The fields, Fortran images with the garbage slot, diag pool: depv_dt_lw, depv_dt_sw, depv_dt_bl, depv_dt_cu,
+ * depv_dt_mp, depv_dt_mix, depv_dt_diab, depv_dt_fric (nVertLevels, nCells+1) in PVU/s; dtheta_dt_mp (an
+ * input: the host's microphysics heating, 0.0 until set) and dtheta_dt_mix (written by the call on the cells
+ * 1..nCells), the same shape; depv_dt_diab_pv, depv_dt_fric_pv (nCells+1), the two on the 2-PVU surface.  With
+ * the library's scratch arrays they are allocated, zeroed, at the first mpas_dyc_set_field of one of them or
+ * at mpas_dyc_set_pv_budget with MPAS_DYC_PVB_ON -- a context that asks for neither holds none of them.
+ * mpas_dyc_set_pv_budget(flags): 0 switches the budget off and is always allowed.  A source bit says that the
+ * raw tendency of tend_physics is associated (its scheme runs); a source whose bit is off contributes exact
+ * zeros and is not read.  MPAS_DYC_EINVAL: unknown bits; a source bit without MPAS_DYC_PVB_ON.
+ * MPAS_DYC_ESTATE: MPAS_DYC_PVB_ON while mpas_dyc_set_pv is off.  On a MPAS_DYC_HOST_ONLY context the mask is
+ * kept and nothing is allocated. */
+int mpas_dyc_set_pv_budget(mpas_dyc_ctx* ctx, int32_t flags);
+/* The reference's pv_diagnostics_compute when a budget field is written: mpas_dyc_pv_diagnostics (unchanged)
+ * and then, on the same time level,
+ *   1. on a context that has exchange lists, the halos the reference exchanges (:1592-1605): the raw theta
+ *      tendencies whose bits are set, dtheta_dt_mp, tend_u_phys, tend.u_euler and tend.w_euler (COLLECTIVE);
+ *   2. dtheta_dt_mix = tend.theta_euler / (1 + rvord qv) on all cells (:1578-1584), then its halo;
+ *   3. F = tend_u_phys + tend.u_euler / rho_edge on all edges (:1477-1481; without diag.tend_u_phys, which
+ *      only mpas_dyc_set_todynamics allocates, the literal 0.0 takes its place) and tend.w_euler over the
+ *      density at the interfaces on all cells (:1492-1501);
+ *   4. calc_vertical_curl of F on all vertices (:1113-1137): a vertex sums its valid edges in ascending
+ *      local edge index, as the reference's edge loop reaches them; mpas_reconstruct of F on the owned cells;
+ *   5. on the owned cells depv_dt_{lw,sw,bl,cu,mp,mix} = ((curl u + 2 Omega) / rho) . grad(source) 1e6 and
+ *      their sum depv_dt_diab = ((((lw + sw) + bl) + cu) + mp) + mix (:1386-1473; mix is guarded by
+ *      dtheta_dt_mp's association as in the reference, :1460, which always holds here), and depv_dt_fric =
+ *      curl(F, uncoupled tend_w) . (grad theta / rho) 1e6 (:1503-1529);
+ *   6. depv_dt_diab_pv and depv_dt_fric_pv: interp_pv with the iLev_DT and ertel_pv just computed (:786-824).
+ *      The fill gives iLev_DT = 0 or >= 2, never 1; for 1 the reference's interp_pv would read level 0, the
+ *      element before the column in memory.  Should a column hold 1 all the same, this library reads level 1
+ *      in its place (the lower level clamped into the column): defined differently from the reference
+ *      (and from the numpy restatement, which repeats the reference's read) there.
+ * fp64 in the Fortran's operand order, no contraction: the reference's bits below level nVertLevels (there
+ * mpas_dyc_pv_diagnostics' deviation carries over: dv_dz takes velCellm), with two more defined deviations.
+ * The reference overwrites tend_u_phys and tend.w_euler in place (:1479, :1496-1501); this library leaves
+ * both untouched and works in scratch, so a second call gives the same bits and the next step's
+ * physics_get_tend accumulation is not polluted.  And the outputs are written on the owned cells only: the
+ * reference's whole-array depv_dt_diab sum also covers halo columns that nothing computed.
+ * It reads what mpas_dyc_pv_diagnostics reads, the tendencies named above, diag.rho_edge, mesh.dcEdge,
+ * areaTriangle, verticesOnEdge, edgesOnVertex and coeffs_reconstruct.  SYNCHRONOUS like
+ * mpas_dyc_pv_diagnostics; always eager, never part of the step's captured graph.  Under
+ * mpas_dyc_set_profile its milliseconds, the PV diagnostics included, are mpas_dyc_get_profile out[13].
+ * Switch off: does nothing and allocates nothing.  Errors: those of mpas_dyc_pv_diagnostics, and
+ * MPAS_DYC_ESTATE when mpas_dyc_set_pv is off; when mesh.coeffs_reconstruct was neither computed
+ * (mpas_dyc_init_reconstruct) nor set, or mesh.areaTriangle never set; when a source bit is set but its raw
+ * array was never allocated -- each with a message that names the field. */
+int mpas_dyc_pv_budget_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level);
 /* The output-time half of the reference's convective diagnostics (diagnostics/convective_diagnostics.F,
  * Registry_convective.xml), on the device (convcompute.hip): convective_diagnostics_compute (:227-487) with
  * getcape (:595-1037), so a run that writes cape, cin or the helicities need not copy theta_m, qv, exner,
@@ -795,7 +850,9 @@ double mpas_dyc_acoustic_bytes(const mpas_dyc_ctx* ctx);
  * included); out[10] = the sweeps of the last mpas_dyc_pv_diagnostics' fill that changed something, the
  * most over the blocks.
  * out[11] = milliseconds of the last mpas_dyc_convective_diagnostics called with the profile on.
- * out[12] = the same for the last mpas_dyc_physics_get_tend called with the profile on. */
+ * out[12] = the same for the last mpas_dyc_physics_get_tend called with the profile on.
+ * out[13] = the same for the last mpas_dyc_pv_budget_diagnostics called with the profile on (the PV
+ * diagnostics it runs first included). */
 int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on);
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n);
 /* The plan key of the exchange whose RCCL group was enqueued last ("warm_rccl <key>" while the

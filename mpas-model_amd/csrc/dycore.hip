@@ -37,6 +37,7 @@
 #include "kessler.hip"
 #include "isobaric.hip"
 #include "pv.hip"
+#include "pvbudget.hip"
 #include "convcompute.hip"
 
 using namespace mpas;
@@ -50,7 +51,7 @@ enum Target { T_NONE, T_CELL, T_EDGE, T_VERTEX, T_SMALL };  // int index semanti
 // coefficients read (mpas_dyc_model_init, mpas_dyc_init_reconstruct).  The others belong to a step hook
 // (physics_host.hip) and are allocated together, zeroed, by alloc_group: when the hook is switched on,
 // or at the first set_field of one of them.
-enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP, G_ISOBARIC, G_PV, G_CONVCOMPUTE, G_TODYN };
+enum Group { G_ALWAYS, G_ON_SET, G_IAU_INCR, G_IAU_SUMS, G_CONVDIAG, G_MICROP, G_ISOBARIC, G_PV, G_CONVCOMPUTE, G_TODYN, G_PVB };
 // all_blocks: a first set_field completes the group on every block (false: on that block only).
 // hidden: mpas_dyc_block_field_bytes reports 0 until the field is allocated -- the fields are held
 // only by a context that asked for them.
@@ -64,6 +65,7 @@ constexpr struct { bool all_blocks, hidden; } GROUPS[] = {
     {true, true},    // G_PV: the PV diagnostics' outputs and the three mesh vector arrays they read
     {true, true},    // G_CONVCOMPUTE: cape, cin, the helicities and the surface / 1 km / 6 km fields
     {true, true},    // G_TODYN: physics_get_tend's raw tendencies, edge projections, tend_u_phys, mesh.east / north
+    {true, true},    // G_PVB: the PV budget's outputs, dtheta_dt_mp / dtheta_dt_mix and its scratch arrays
 };
 
 struct Field {
@@ -120,6 +122,7 @@ struct Block {
   int* iso_fail = nullptr;             // compute_slp's failure word of the block (isobaric.hip), on the device
   PvBlock pv;                          // the PV diagnostics' derived table and fill buffers (pv.hip)
   int todyn_set = 0;                   // TODYN_SET_*: mesh.east / north have been set (todynamics.hip)
+  bool rec_set = false;                // mesh.coeffs_reconstruct has been set or computed (the PV budget reads it)
   // maxEdges / maxEdges2 as the host declared them (the mesh file's dimensions; Fortran images and
   // h_eoc use these strides).  d.maxEdges / d.maxEdges2 are the strides the kernels index with:
   // max(nEdgesOnCell) and the edgesOnEdge slots the kernels need after pack_mesh
@@ -313,6 +316,7 @@ struct mpas_dyc_ctx {
   IauState iau;                         // incremental analysis update (mpas_dyc_set_iau; iau.hip)
   IsoState iso;                         // the isobaric diagnostics (mpas_dyc_set_isobaric; isobaric.hip)
   PvState pv;                           // the PV diagnostics (mpas_dyc_set_pv; pv.hip)
+  PvbState pvb;                         // the PV budget (mpas_dyc_set_pv_budget; pvbudget.hip)
   ConvState conv;                       // cape, cin, helicity, surface fields (mpas_dyc_set_convective; convcompute.hip)
   ConvDiagState convdiag;               // the convective running maxima (mpas_dyc_set_diag_update; convdiag.hip)
   MicropState microp;                   // the device microphysics (mpas_dyc_set_microphysics; kessler.hip)
@@ -606,6 +610,19 @@ void build_registry(Block& c) {
   for (const char* n : {"rublten_Edge", "rucuten_Edge"}) add(c, "tend_physics", n, L_EDGE, K).group = G_TODYN;
   add(c, "diag", "tend_u_phys", L_EDGE, K).group = G_TODYN;
   for (const char* n : {"east", "north"}) add(c, "mesh", n, L_CELL, 3).group = G_TODYN;
+  // the PV budget (Registry_pv.xml, diag; pvbudget.hip): depv_dt_lw / sw / bl / cu / mp / mix / diab / fric, the
+  // input dtheta_dt_mp (the host's, 0.0 until set) and dtheta_dt_mix ((K, nCells + 1) each), depv_dt_diab_pv and
+  // depv_dt_fric_pv (nCells + 1), and the library's own scratch: the uncoupled tend_w_euler (K + 1, nCells + 1),
+  // tend_u_phys + tend_u_euler / rho_edge (K, nEdges + 1), its curl (K, nVertices + 1), its reconstruction
+  // tenduX/Y/Z and the unused zonal / meridional pair (K, nCells + 1); allocated, zeroed, at the first set_field
+  // of one of them or at mpas_dyc_set_pv_budget with MPAS_DYC_PVB_ON
+  for (const char* n : PVB_CELL_FIELDS) add(c, "diag", n, L_CELL, K).group = G_PVB;
+  for (const char* n : {"depv_dt_diab_pv", "depv_dt_fric_pv"}) add(c, "diag", n, L_CELL, 1).group = G_PVB;
+  add(c, "scratch", "pvb_tend_w", L_CELL, K + 1).group = G_PVB;
+  add(c, "scratch", "pvb_tend_u", L_EDGE, K).group = G_PVB;
+  add(c, "scratch", "pvb_curl", L_VERTEX, K).group = G_PVB;
+  for (const char* n : {"pvb_tenduX", "pvb_tenduY", "pvb_tenduZ", "pvb_tenduZonal", "pvb_tenduMerid"})
+    add(c, "scratch", n, L_CELL, K).group = G_PVB;
   // the maxEdges- and maxEdges2-strided mesh arrays (pack_mesh)
   for (const char* n : {"edgesOnCell", "cellsOnCell", "verticesOnCell", "kiteForCell", "coeffs_reconstruct",
                         "edgesOnCell_sign", "defc_a", "defc_b", "zb_cell", "zb3_cell"})
@@ -1905,6 +1922,14 @@ void reconstruct(mpas_dyc_ctx* ctx, const Dims& d, const Ptrs& p, const double* 
   else if (batched(d)) LAUNCH(k_reconstruct_b<7>, d.nCellsSolve, d, p, u);
   else LAUNCH(k_reconstruct, d.nCellsSolve, d, p, u);
 }
+// the same of another edge field into other arrays (the PV budget's tend_u): the kernels take both from
+// their arguments, so the step's own call above is the same launch as before
+void reconstruct_to(mpas_dyc_ctx* ctx, const Dims& d, Ptrs p, const double* u, double* x, double* y, double* z,
+                    double* zonal, double* meridional) {
+  p.uReconstructX = x, p.uReconstructY = y, p.uReconstructZ = z;
+  p.uReconstructZonal = zonal, p.uReconstructMeridional = meridional;
+  reconstruct(ctx, d, p, u);
+}
 
 // atm_srk3 (mpas_atm_time_integration.F:142-1796)
 // atm_bdy_adjust_scalars (6436-6586) at the end of a transport stage: the scalars' halo first
@@ -2785,6 +2810,7 @@ int mpas_dyc_set_block_field(mpas_dyc_ctx* ctx, int32_t block, const char* pool,
   if (f->me || rec_input(*f)) ctx->bnd_ready = false;  // pack_mesh copies the new image for the kernels
   coefs_touched(ctx, *f);
   pv_touch(b, *f);
+  if (f->pool == "mesh" && f->name == "coeffs_reconstruct") b.rec_set = true;
   if (f->is_int && f->target != T_NONE) {
     // MPAS 1-based -> device 0-based; out-of-range / 0 -> garbage slot
     const int64_t n = field_elems(b, *f);
@@ -3509,6 +3535,7 @@ int mpas_dyc_init_reconstruct(mpas_dyc_ctx* ctx) {
       rc = MPAS_DYC_EINVAL;
       break;
     }
+    b.rec_set = true;
   }
   if (rc == MPAS_DYC_EHIP) ctx->err = "mpas_dyc_init_reconstruct: HIP error";
   (void)hipFree(bad);
@@ -3636,7 +3663,7 @@ int mpas_dyc_set_profile(mpas_dyc_ctx* ctx, int32_t on) {
 
 int mpas_dyc_get_profile(mpas_dyc_ctx* ctx, double* out, int32_t n) {
   if (!ctx || !out || n < 1) return MPAS_DYC_EINVAL;
-  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : i == 8 ? ctx->iso.ms : i == 9 ? ctx->pv.ms : i == 10 ? (double)ctx->pv.sweeps : i == 11 ? ctx->conv.ms : i == 12 ? ctx->todyn.ms : 0.0;
+  for (int i = 0; i < n; ++i) out[i] = i < 5 ? ctx->prof_out[i] : i == 5 ? (double)ctx->graph_captures : i == 6 ? ctx->convdiag.ms : i == 7 ? ctx->microp.ms : i == 8 ? ctx->iso.ms : i == 9 ? ctx->pv.ms : i == 10 ? (double)ctx->pv.sweeps : i == 11 ? ctx->conv.ms : i == 12 ? ctx->todyn.ms : i == 13 ? ctx->pvb.ms : 0.0;
   return MPAS_DYC_OK;
 }
 

@@ -1,8 +1,8 @@
 // Host side of the step's physics hooks: the incremental analysis update (kernels: iau.hip), the coupling
 // of the physics tendencies (physics_get_tend: todynamics.hip), the
 // convective running maxima (convdiag.hip), the device microphysics (kessler.hip), the isobaric output
-// diagnostics (isobaric.hip), the PV diagnostics (pv.hip) and the output-time convective diagnostics
-// (convcompute.hip; the last three are not part of the step, but hooks of the same shape).  Per hook: what
+// diagnostics (isobaric.hip), the PV diagnostics (pv.hip) with their budget (pvbudget.hip) and the output-time
+// convective diagnostics (convcompute.hip; the last four are not part of the step, but hooks of the same shape).  Per hook: what
 // enqueues its kernels, and its entry points of include/mpas_dycore.h.  A hook's state struct
 // (mpas_dyc_ctx::iau / todyn / convdiag / microp / iso / pv / conv, Block::cv / pv) stands next to its kernels' argument struct; its
 // fields are a Group of the registry (dycore.hip build_registry), allocated by alloc_group.
@@ -386,6 +386,124 @@ int pv_run(mpas_dyc_ctx* ctx, int tl, bool lists) {
   return MPAS_DYC_OK;
 }
 
+// What mpas_dyc_pv_diagnostics and mpas_dyc_pv_budget_diagnostics do before they enqueue: the group, the mesh
+// inputs of every block, the packed strides and the derived table.  `lists`: a block has exchange lists
+int pv_check_prepare(mpas_dyc_ctx* ctx, const char* entry, bool* lists) {
+  if (!group_ready(ctx, G_PV)) CHK(alloc_group(ctx, G_PV));
+  *lists = false;
+  for (auto& b : ctx->blk) {
+    if (const char* missing = pv_missing_input(b)) {
+      ctx->err = std::string(entry) + ": " + missing + " not set";
+      return MPAS_DYC_ESTATE;
+    }
+    *lists = *lists || !b.xl.empty();
+  }
+  if (!ctx->bnd_ready) CHK(compute_bnd(ctx));  // the packed strides the table is indexed with
+  for (auto& b : ctx->blk) CHK(pv_prepare(ctx, b));
+  return MPAS_DYC_OK;
+}
+
+// ---- Ertel PV budget ----
+// an input of block b that the budget with mask `flags` needs and that was never set or allocated, or nullptr
+const char* pvb_missing_input(Block& b, int flags) {
+  if (!b.rec_set) return "mesh.coeffs_reconstruct";
+  if (!find(b, "mesh", "areaTriangle")->buf[0]) return "mesh.areaTriangle";
+  for (const auto& r : PVB_RAW)
+    if ((flags & r.bit) && !find(b, "tend_physics", r.name)->buf[0]) return r.name;
+  return nullptr;
+}
+
+// atm_compute_pvBudget_diagnostics on time level tl of every block (pvbudget.hip) after pv_run of the same
+// level, `lists`: with its halo exchanges (:1592-1605; dtheta_dt_mix's after the kernel that forms it)
+int pvb_run(mpas_dyc_ctx* ctx, int tl, bool lists) {
+  const int fl = ctx->pvb.flags, layers = 7;
+  const bool phys = find(ctx->blk[0], "diag", "tend_u_phys")->buf[0] != nullptr;  // a group: the same on every block
+  if (lists) {
+    for (const auto& r : PVB_RAW)
+      if (fl & r.bit) CHK(mpas_dyc_halo_exchange(ctx, "tend_physics", r.name, 1, layers));
+    CHK(mpas_dyc_halo_exchange(ctx, "diag", "dtheta_dt_mp", 1, layers));
+    if (phys) CHK(mpas_dyc_halo_exchange(ctx, "diag", "tend_u_phys", 1, layers));
+    CHK(mpas_dyc_halo_exchange(ctx, "tend", "u_euler", 1, layers));
+    CHK(mpas_dyc_halo_exchange(ctx, "tend", "w_euler", 1, layers));
+  }
+  auto grid = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 65536))); };
+  for (auto& b : ctx->blk) {
+    const Dims& d = b.d;
+    if (d.nCells <= 0) continue;
+    hipLaunchKernelGGL(k_pvb_cells, grid((int64_t)d.nCells * (d.K + 1)), dim3(256), 0, ctx->stream, (int64_t)d.nCells, d.K,
+                       P<const double>(ctx, b, "tend", "theta_euler"),
+                       P<const double>(ctx, b, "state", "scalars", tl) + (int64_t)ctx->index_qv * (d.nCells + 1) * d.K,
+                       P<const double>(ctx, b, "diag", "rho"), P<const double>(ctx, b, "tend", "w_euler"),
+                       P<double>(ctx, b, "diag", "dtheta_dt_mix"), P<double>(ctx, b, "scratch", "pvb_tend_w"));
+  }
+  HIPCHK(hipGetLastError());
+  if (lists) CHK(mpas_dyc_halo_exchange(ctx, "diag", "dtheta_dt_mix", 1, layers));
+  const std::vector<Ptrs> ptrs = block_ptrs(ctx);
+  for (size_t ib = 0; ib < ctx->blk.size(); ++ib) {
+    Block& b = ctx->blk[ib];
+    const Dims& d = b.d;
+    double* tend_u = P<double>(ctx, b, "scratch", "pvb_tend_u");
+    if (d.nEdges > 0)
+      hipLaunchKernelGGL(k_pvb_edges, grid((int64_t)d.nEdges * d.K), dim3(256), 0, ctx->stream, (int64_t)d.nEdges * d.K,
+                         phys ? P<const double>(ctx, b, "diag", "tend_u_phys") : nullptr,
+                         P<const double>(ctx, b, "tend", "u_euler"), P<const double>(ctx, b, "diag", "rho_edge"), tend_u);
+    if (d.nVertices > 0) {
+      PvbCurl a{};
+      a.nVertices = d.nVertices, a.nEdges = d.nEdges, a.K = d.K;
+      a.edgesOnVertex = P<const int>(ctx, b, "mesh", "edgesOnVertex");
+      a.verticesOnEdge = P<const int>(ctx, b, "mesh", "verticesOnEdge");
+      a.dcEdge = P<const double>(ctx, b, "mesh", "dcEdge");
+      a.areaTriangle = P<const double>(ctx, b, "mesh", "areaTriangle");
+      a.u = tend_u;
+      a.curl = P<double>(ctx, b, "scratch", "pvb_curl");
+      hipLaunchKernelGGL(k_pvb_curl, dim3((unsigned)((d.nVertices + PV_WAVES - 1) / PV_WAVES)), dim3(PV_THREADS), 0,
+                         ctx->stream, a);
+    }
+    if (d.nCellsSolve <= 0) continue;
+    reconstruct_to(ctx, d, ptrs[ib], tend_u, P<double>(ctx, b, "scratch", "pvb_tenduX"),
+                   P<double>(ctx, b, "scratch", "pvb_tenduY"), P<double>(ctx, b, "scratch", "pvb_tenduZ"),
+                   P<double>(ctx, b, "scratch", "pvb_tenduZonal"), P<double>(ctx, b, "scratch", "pvb_tenduMerid"));
+    PvBudget a{};
+    a.nCellsSolve = d.nCellsSolve, a.K = d.K, a.ME = d.maxEdges;
+    a.nEdgesOnCell = P<const int>(ctx, b, "mesh", "nEdgesOnCell");
+    a.cellsOnCell = P<const int>(ctx, b, "mesh", "cellsOnCell");
+    a.verticesOnCell = P<const int>(ctx, b, "mesh", "verticesOnCell");
+    a.geom = b.pv.geom;
+    a.zgrid = P<const double>(ctx, b, "mesh", "zgrid");
+    a.w = P<const double>(ctx, b, "state", "w", tl);
+    a.theta = P<const double>(ctx, b, "diag", "theta");
+    a.rho = P<const double>(ctx, b, "diag", "rho");
+    a.vorticity = P<const double>(ctx, b, "diag", "vorticity");
+    a.ux = P<const double>(ctx, b, "diag", "uReconstructX");
+    a.uy = P<const double>(ctx, b, "diag", "uReconstructY");
+    a.uz = P<const double>(ctx, b, "diag", "uReconstructZ");
+    for (int j = 0; j < 4; ++j) a.src[j] = (fl & PVB_RAW[j].bit) ? P<const double>(ctx, b, "tend_physics", PVB_RAW[j].name) : nullptr;
+    a.src[4] = P<const double>(ctx, b, "diag", "dtheta_dt_mp");
+    a.src[5] = P<const double>(ctx, b, "diag", "dtheta_dt_mix");  // guarded by dtheta_dt_mp's association (:1460)
+    a.tend_w = P<const double>(ctx, b, "scratch", "pvb_tend_w");
+    a.curl = P<const double>(ctx, b, "scratch", "pvb_curl");
+    a.tx = P<const double>(ctx, b, "scratch", "pvb_tenduX");
+    a.ty = P<const double>(ctx, b, "scratch", "pvb_tenduY");
+    a.tz = P<const double>(ctx, b, "scratch", "pvb_tenduZ");
+    for (int j = 0; j < PVB_NSRC; ++j) a.out[j] = P<double>(ctx, b, "diag", PVB_CELL_FIELDS[j]);
+    a.diab = P<double>(ctx, b, "diag", "depv_dt_diab");
+    a.fric = P<double>(ctx, b, "diag", "depv_dt_fric");
+    hipLaunchKernelGGL(k_pvb_budget, dim3((unsigned)((d.nCellsSolve + PV_WAVES - 1) / PV_WAVES)), dim3(PV_THREADS), 0,
+                       ctx->stream, a);
+    PvbInterp q{};
+    q.nCellsSolve = d.nCellsSolve, q.K = d.K;
+    q.iLev_DT = P<const int>(ctx, b, "diag", "iLev_DT");
+    q.latCell = P<const double>(ctx, b, "mesh", "latCell");
+    q.ertel_pv = P<const double>(ctx, b, "diag", "ertel_pv");
+    q.diab = a.diab, q.fric = a.fric;
+    q.diab_pv = P<double>(ctx, b, "diag", "depv_dt_diab_pv");
+    q.fric_pv = P<double>(ctx, b, "diag", "depv_dt_fric_pv");
+    hipLaunchKernelGGL(k_pvb_interp, dim3((unsigned)((d.nCellsSolve + 255) / 256)), dim3(256), 0, ctx->stream, q);
+  }
+  HIPCHK(hipGetLastError());
+  return MPAS_DYC_OK;
+}
+
 // ---- cape, cin, storm-relative helicity and the surface / 1 km / 6 km fields ----
 // convective_diagnostics_compute with the context's mask on time level tl of every block: the shear and
 // helicity kernel, then the parcel ascent if cape or cin is asked for
@@ -628,18 +746,60 @@ int mpas_dyc_pv_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level) {
   }
   if (!ctx->pv.on) return MPAS_DYC_OK;
   HIPCHK(hipSetDevice(ctx->device));
-  if (!group_ready(ctx, G_PV)) CHK(alloc_group(ctx, G_PV));
   bool lists = false;
-  for (auto& b : ctx->blk) {
-    if (const char* missing = pv_missing_input(b)) {
-      ctx->err = std::string("mpas_dyc_pv_diagnostics: ") + missing + " not set";
+  CHK(pv_check_prepare(ctx, "mpas_dyc_pv_diagnostics", &lists));
+  return timed_on_stream(ctx, ctx->pv.ms, [&]() -> int { return pv_run(ctx, time_level, lists); });
+}
+
+int mpas_dyc_set_pv_budget(mpas_dyc_ctx* ctx, int32_t flags) {
+  if (!ctx) return MPAS_DYC_EINVAL;
+  if (flags & ~PVB_ALL) {
+    ctx->err = "mpas_dyc_set_pv_budget: unknown flag bits";
+    return MPAS_DYC_EINVAL;
+  }
+  if (flags && !(flags & PVB_ON)) {
+    ctx->err = "mpas_dyc_set_pv_budget: a source bit without MPAS_DYC_PVB_ON";
+    return MPAS_DYC_EINVAL;
+  }
+  if (flags && !ctx->pv.on) {
+    ctx->err = "mpas_dyc_set_pv_budget: MPAS_DYC_PVB_ON while mpas_dyc_set_pv is off (the budget reads its outputs)";
+    return MPAS_DYC_ESTATE;
+  }
+  ctx->pvb.flags = flags;
+  if (ctx->host_only || !flags) return MPAS_DYC_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!group_ready(ctx, G_PVB)) CHK(alloc_group(ctx, G_PVB));
+  return MPAS_DYC_OK;
+}
+
+int mpas_dyc_pv_budget_diagnostics(mpas_dyc_ctx* ctx, int32_t time_level) {
+  if (!ctx || (time_level != 1 && time_level != 2)) return MPAS_DYC_EINVAL;
+  CHK(require_device(ctx));
+  if (ctx->tail_pending) {
+    ctx->err = "mpas_dyc_pv_budget_diagnostics between mpas_dyc_timestep and mpas_dyc_finish_step";
+    return MPAS_DYC_ESTATE;
+  }
+  if (!ctx->pvb.flags) return MPAS_DYC_OK;
+  if (!ctx->pv.on) {
+    ctx->err = "mpas_dyc_pv_budget_diagnostics: mpas_dyc_set_pv is off (the budget reads its outputs)";
+    return MPAS_DYC_ESTATE;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  for (auto& b : ctx->blk)
+    if (const char* missing = pvb_missing_input(b, ctx->pvb.flags)) {
+      ctx->err = std::string("mpas_dyc_pv_budget_diagnostics: ") + missing +
+                 (std::string(missing) == "mesh.coeffs_reconstruct" ? " not set (mpas_dyc_init_reconstruct)"
+                  : std::string(missing).rfind("mesh.", 0) == 0    ? " not set"
+                                                                    : " never allocated (tend_physics)");
       return MPAS_DYC_ESTATE;
     }
-    lists = lists || !b.xl.empty();
-  }
-  if (!ctx->bnd_ready) CHK(compute_bnd(ctx));  // the packed strides the table is indexed with
-  for (auto& b : ctx->blk) CHK(pv_prepare(ctx, b));
-  return timed_on_stream(ctx, ctx->pv.ms, [&]() -> int { return pv_run(ctx, time_level, lists); });
+  bool lists = false;
+  CHK(pv_check_prepare(ctx, "mpas_dyc_pv_budget_diagnostics", &lists));
+  if (!group_ready(ctx, G_PVB)) CHK(alloc_group(ctx, G_PVB));
+  return timed_on_stream(ctx, ctx->pvb.ms, [&]() -> int {
+    CHK(pv_run(ctx, time_level, lists));
+    return pvb_run(ctx, time_level, lists);
+  });
 }
 
 int mpas_dyc_set_isobaric(mpas_dyc_ctx* ctx, int32_t flags) {

@@ -7,8 +7,8 @@
 //       that is connected to the near-surface seeds
 //   u_pv, v_pv, theta_pv, vort_pv on the owned cells: interp_pv_diagnostics / interp_pv (:718-784, :826-899)
 // The halo exchanges between them are the host's (physics_host.hip pv_run).  The PV budget (calc_pvBudget,
-// interp_pvBudget_diagnostics) needs the physics suites' tendencies and stays with the host; floodFill_strato
-// is never called by the reference.
+// interp_pvBudget_diagnostics) is pvbudget.hip, which reads this file's table, pv_dot, pv_vert and pv_interp;
+// floodFill_strato is never called by the reference.
 //
 // k_pv_geom: everything of calc_gradxu_cell / calc_grad_cell that does not depend on the level, once per
 // owned cell, with the operations the Fortran repeats at every level: the two normalised tangent vectors;

@@ -275,6 +275,17 @@ module atm_time_integration
          type(c_ptr), value :: ctx
          integer(c_int32_t), value :: time_level
       end function
+      integer(c_int) function mpas_dyc_set_pv_budget(ctx, flags) bind(C, name='mpas_dyc_set_pv_budget')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: flags
+      end function
+      integer(c_int) function mpas_dyc_pv_budget_diagnostics(ctx, time_level) &
+            bind(C, name='mpas_dyc_pv_budget_diagnostics')
+         import :: c_int, c_ptr, c_int32_t
+         type(c_ptr), value :: ctx
+         integer(c_int32_t), value :: time_level
+      end function
       integer(c_int) function mpas_dyc_set_convective(ctx, flags) bind(C, name='mpas_dyc_set_convective')
          import :: c_int, c_ptr, c_int32_t
          type(c_ptr), value :: ctx
@@ -349,6 +360,14 @@ module atm_time_integration
    logical, save, private :: pv_mesh_sent = .false.
    character(len=32), dimension(6), parameter, private :: pv_outputs = [character(len=32) :: &
       'ertel_pv', 'iLev_DT', 'u_pv', 'v_pv', 'theta_pv', 'vort_pv']
+   ! the PV budget (atm_dycore_pv_budget_diagnostics): areaTriangle is on the device; the raw theta tendencies in
+   ! the bit order of the MPAS_DYC_PVB_* mask's sources (bit i of the mask); what is downloaded
+   logical, save, private :: pvb_mesh_sent = .false.
+   character(len=32), dimension(4), parameter, private :: pvb_raw = [character(len=32) :: &
+      'rthratenlw', 'rthratensw', 'rthblten', 'rthcuten']
+   character(len=32), dimension(11), parameter, private :: pvb_outputs = [character(len=32) :: &
+      'depv_dt_lw', 'depv_dt_sw', 'depv_dt_bl', 'depv_dt_cu', 'depv_dt_mp', 'depv_dt_mix', 'depv_dt_diab', &
+      'depv_dt_fric', 'dtheta_dt_mix', 'depv_dt_diab_pv', 'depv_dt_fric_pv']
    ! the output-time convective diagnostics (atm_dycore_convective_diagnostics): bit i-1 of the MPAS_DYC_CONV_* mask
    character(len=32), dimension(14), parameter, private :: conv_outputs = [character(len=32) :: &
       'cape', 'cin', 'lcl', 'lfc', 'srh_0_1km', 'srh_0_3km', 'uzonal_surface', 'uzonal_1km', 'uzonal_6km', &
@@ -696,7 +715,7 @@ module atm_time_integration
    ! localVerticalUnitVectors, edgeNormalVectors) and areaCell; every call runs mpas_dyc_pv_diagnostics on
    ! time level 1 and downloads ertel_pv, iLev_DT, u_pv, v_pv, theta_pv and vort_pv into the diag pool.
    ! The 3-D state stays on the device.  The call exchanges halos: every task calls it.  The PV budget
-   ! (atm_compute_pvBudget_diagnostics) needs the physics' tendencies and stays with the host.
+   ! (atm_compute_pvBudget_diagnostics) is atm_dycore_pv_budget_diagnostics below.
    subroutine atm_dycore_pv_diagnostics(domain)
       type (domain_type), intent(inout) :: domain
       type (block_type), pointer :: block
@@ -731,6 +750,96 @@ module atm_time_integration
          block => block % next
       end do
    end subroutine atm_dycore_pv_diagnostics
+
+   ! pv_diagnostics_compute when a depv_dt_* field is written: atm_compute_pv_diagnostics and
+   ! atm_compute_pvBudget_diagnostics(state, 1, diag, mesh, tend, tend_physics) (:1291-1613) on the device.
+   ! This module couples the physics on the host (physics_get_tend), so the budget's physics inputs live in
+   ! the pools: every call uploads the raw theta tendencies that are associated (their bits of the
+   ! MPAS_DYC_PVB_* mask follow from the association, as the reference's tests do), diag's dtheta_dt_mp and
+   ! tend_u_phys; the first call also uploads areaTriangle.  tend.u_euler / w_euler / theta_euler and rho_edge
+   ! are the device's own.  It then downloads the PV diagnostics' six outputs, the eight depv_dt_* terms,
+   ! dtheta_dt_mix and the two *_pv fields into the diag pool.  Unlike the reference it leaves tend_u_phys
+   ! and tend.w_euler as they are.  The call exchanges halos: every task calls it.
+   subroutine atm_dycore_pv_budget_diagnostics(domain)
+      type (domain_type), intent(inout) :: domain
+      type (block_type), pointer :: block
+      type (mpas_pool_type), pointer :: mesh, diag, tend_physics
+      integer :: ib, i
+      integer(c_int32_t) :: flags
+      logical :: sent
+
+      if (.not. c_associated(dyc)) return
+      call check(dyc, mpas_dyc_set_pv(dyc, 1_c_int32_t), 'mpas_dyc_set_pv')
+      flags = 1
+      block => domain % blocklist
+      ib = 0
+      do while (associated(block))
+         call mpas_pool_get_subpool(block % structs, 'mesh', mesh)
+         call mpas_pool_get_subpool(block % structs, 'diag', diag)
+         call mpas_pool_get_subpool(block % structs, 'tend_physics', tend_physics)
+         if (.not. pvb_mesh_sent) then
+            if (.not. pv_mesh_sent) then
+               call xfer(dyc, ib, mesh, 'mesh', 'cellTangentPlane', 1, 1, UP, .true.)
+               call xfer(dyc, ib, mesh, 'mesh', 'localVerticalUnitVectors', 1, 1, UP, .true.)
+               call xfer(dyc, ib, mesh, 'mesh', 'edgeNormalVectors', 1, 1, UP, .true.)
+               call xfer(dyc, ib, mesh, 'mesh', 'areaCell', 1, 1, UP, .true.)
+            end if
+            call xfer(dyc, ib, mesh, 'mesh', 'areaTriangle', 1, 1, UP, .true.)
+         end if
+         if (associated(tend_physics)) then
+            do i = 1, size(pvb_raw)
+               call send_columns(dyc, ib, tend_physics, 'tend_physics', trim(pvb_raw(i)), sent)
+               if (sent) flags = ior(flags, ishft(2_c_int32_t, i - 1))
+            end do
+         end if
+         call send_columns(dyc, ib, diag, 'diag', 'tend_u_phys', sent)
+         ib = ib + 1
+         block => block % next
+      end do
+      pv_mesh_sent = .true.
+      pvb_mesh_sent = .true.
+      call check(dyc, mpas_dyc_set_pv_budget(dyc, flags), 'mpas_dyc_set_pv_budget')   ! allocates dtheta_dt_mp
+      block => domain % blocklist
+      ib = 0
+      do while (associated(block))
+         call mpas_pool_get_subpool(block % structs, 'diag', diag)
+         call xfer(dyc, ib, diag, 'diag', 'dtheta_dt_mp', 1, 1, UP, .false.)
+         ib = ib + 1
+         block => block % next
+      end do
+      call check(dyc, mpas_dyc_pv_budget_diagnostics(dyc, 1_c_int32_t), 'mpas_dyc_pv_budget_diagnostics')
+      block => domain % blocklist
+      ib = 0
+      do while (associated(block))
+         call mpas_pool_get_subpool(block % structs, 'diag', diag)
+         do i = 1, size(pv_outputs)
+            call xfer(dyc, ib, diag, 'diag', trim(pv_outputs(i)), 1, 1, DOWN, .false.)
+         end do
+         do i = 1, size(pvb_outputs)
+            call xfer(dyc, ib, diag, 'diag', trim(pvb_outputs(i)), 1, 1, DOWN, .false.)
+         end do
+         ib = ib + 1
+         block => block % next
+      end do
+   end subroutine atm_dycore_pv_budget_diagnostics
+
+   ! A (nVertLevels, n+1) pool array that is associated -> its device field, which a first upload allocates
+   ! with its group (so xfer's size test, which sees 0 bytes until then, cannot be used); sent = it was
+   subroutine send_columns(ctx, ib, pool, pname, name, sent)
+      type(c_ptr), intent(in) :: ctx
+      integer, intent(in) :: ib
+      type (mpas_pool_type), intent(in) :: pool
+      character(len=*), intent(in) :: pname, name
+      logical, intent(out) :: sent
+      real (kind=RKIND), dimension(:,:), pointer :: r2
+      nullify(r2)
+      call mpas_pool_get_array(pool, name, r2)
+      sent = associated(r2)
+      if (.not. sent) return
+      call check(ctx, mpas_dyc_set_block_field(ctx, int(ib, c_int32_t), pname//c_null_char, name//c_null_char, &
+                                               1_c_int32_t, c_loc(r2(1,1)), 8_c_int64_t * size(r2, kind=c_int64_t)), &
+                 'set '//pname//'.'//name)
+   end subroutine send_columns
 
    ! Copy the device state into the host pools' time level 1 (the current one once the caller
    ! has shifted time levels after the step): prognostics, diagnostics, rthdynten / rqvdynten.

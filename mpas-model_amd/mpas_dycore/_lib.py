@@ -32,7 +32,8 @@ EXPORTS = (
     "mpas_dyc_diag_update", "mpas_dyc_diag_reset", "mpas_dyc_folded_passes", "mpas_dyc_set_microphysics",
     "mpas_dyc_microphysics", "mpas_dyc_set_isobaric", "mpas_dyc_isobaric_diagnostics", "mpas_dyc_set_pv",
     "mpas_dyc_pv_diagnostics", "mpas_dyc_set_convective", "mpas_dyc_convective_diagnostics",
-    "mpas_dyc_set_todynamics", "mpas_dyc_physics_get_tend",
+    "mpas_dyc_set_todynamics", "mpas_dyc_physics_get_tend", "mpas_dyc_set_pv_budget",
+    "mpas_dyc_pv_budget_diagnostics",
 )
 HOST_ONLY = -2  # MPAS_DYC_HOST_ONLY: planner-only context
 PRINT_GLOBAL_MINMAX_VEL, PRINT_DETAILED_MINMAX_VEL, PRINT_GLOBAL_MINMAX_SCA = 1, 2, 4
@@ -53,6 +54,9 @@ CONV_ALL = 16383
 (TODYN_PBL, TODYN_PBL_MYNN, TODYN_CU, TODYN_CU_KF, TODYN_CU_WINDS, TODYN_LW, TODYN_SW,
  TODYN_RQVDYNTEN) = (1 << i for i in range(8))
 TODYN_ALL = 255
+# MPAS_DYC_PVB_*: the switch and the associated raw theta tendencies of mpas_dyc_set_pv_budget
+PVB_ON, PVB_LW, PVB_SW, PVB_BL, PVB_CU = 1, 2, 4, 8, 16
+PVB_ALL = 31
 CELL, EDGE, VERTEX = 0, 1, 2
 SEND, RECV = 0, 1
 
@@ -159,6 +163,8 @@ def load() -> C.CDLL:
     lib.mpas_dyc_isobaric_diagnostics.argtypes = [vp, i32]
     lib.mpas_dyc_set_pv.argtypes = [vp, i32]
     lib.mpas_dyc_pv_diagnostics.argtypes = [vp, i32]
+    lib.mpas_dyc_set_pv_budget.argtypes = [vp, i32]
+    lib.mpas_dyc_pv_budget_diagnostics.argtypes = [vp, i32]
     lib.mpas_dyc_set_convective.argtypes = [vp, i32]
     lib.mpas_dyc_convective_diagnostics.argtypes = [vp, i32]
     lib.mpas_dyc_set_todynamics.argtypes = [vp, i32, i32, i32, i32, i32, i32]

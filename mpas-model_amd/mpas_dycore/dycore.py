@@ -38,7 +38,8 @@ _SKIP = set(STATE_INPUTS) | set(DIAG_INPUTS) | {"xCell", "yCell", "zCell", "xEdg
                                                 "meshDensity", "indexToCellID", "deriv_two", "zb", "zb3",
                                                 "w_velocity_max", "wind_speed_level1_max", "updraft_helicity_max",
                                                 *F.MICROP_FIELD, *F.ISO_CELL_FIELDS, *F.ISO_VERTEX_FIELDS,
-                                                *F.ISO_LEVEL_TABLES, *F.PV_OUTPUTS, *F.PV_MESH_INPUTS, *F.CONV_OUTPUTS}
+                                                *F.ISO_LEVEL_TABLES, *F.PV_OUTPUTS, *F.PV_MESH_INPUTS, *F.CONV_OUTPUTS,
+                                                *F.PVB_FIELDS}
 
 
 def _host_allgather_fn(group, nranks: int):
@@ -589,6 +590,52 @@ class Dycore:
         self._check(self.lib.mpas_dyc_get_profile(self.h, out, 11), "get_profile")
         return int(out[10])
 
+    def set_pv_budget(self, on: bool = True, lw: bool | None = None, sw: bool | None = None, bl: bool | None = None,
+                      cu: bool | None = None, flags: int | None = None):
+        """The switch of pv_budget_diagnostics() and the raw theta tendencies that are associated
+        (mpas_dyc_set_pv_budget), after set_pv().  ``lw`` / ``sw`` / ``bl`` / ``cu``: rthratenlw / rthratensw /
+        rthblten / rthcuten take part; None (the default) takes each from the schemes of set_todynamics (LW, SW,
+        PBL -> bl, CU).  A source that is off gives exact zeros and is not read.  ``flags``: the MPAS_DYC_PVB_*
+        mask itself.  On: allocates, zeroed, the diag fields of ``fields.PVB_FIELDS`` -- depv_dt_lw / sw / bl / cu /
+        mp / mix / diab / fric, dtheta_dt_mp (the host's microphysics heating, an input) and dtheta_dt_mix (K per
+        cell), depv_dt_diab_pv and depv_dt_fric_pv (one value per cell) -- and the library's scratch arrays; the
+        curl divides by areaTriangle, which the step itself never reads: it is uploaded here from the case."""
+        from . import pvbudget as B
+        if flags is None:
+            flags = 0
+            if on:
+                dflt = B.flags_from_todynamics(getattr(self, "_todyn_flags", 0))
+                flags = B.ON
+                for given, bit in ((lw, B.LW), (sw, B.SW), (bl, B.BL), (cu, B.CU)):
+                    flags |= bit if (bool(dflt & bit) if given is None else given) else 0
+        self._check(self.lib.mpas_dyc_set_pv_budget(self.h, int(flags)), "set_pv_budget")
+        if flags:
+            for ib, c in enumerate(self.cases):
+                if "areaTriangle" in c:
+                    self.set_raw("mesh", "areaTriangle", to_fortran(c, "areaTriangle"), block=ib)
+
+    def pv_budget_diagnostics(self, time_level: int = 1):
+        """atm_compute_pv_diagnostics and then atm_compute_pvBudget_diagnostics (pv_diagnostics.F:1291-1613) on every
+        block (mpas_dyc_pv_budget_diagnostics): pv_diagnostics() unchanged, then dtheta_dt_mix on all cells and the
+        eight depv_dt_* terms and their two values on the 2-PVU surface on the owned cells, from the raw theta
+        tendencies of set_pv_budget, dtheta_dt_mp, tend_u_phys (0.0 without set_todynamics), tend.u_euler / w_euler
+        / theta_euler and rho_edge as the last step left them: call it after shift_time_levels().  tend_u_phys and
+        tend.w_euler keep their bits (the reference overwrites them).  Synchronous; never part of the step's captured
+        graph; on blocks with exchange lists collective across ranks.  mpas_dycore.pvbudget is its numpy restatement."""
+        self._check(self.lib.mpas_dyc_pv_budget_diagnostics(self.h, int(time_level)), "pv_budget_diagnostics")
+
+    def pv_budget_ms(self, time_level: int = 1) -> float:
+        """Milliseconds of one pv_budget_diagnostics() call between HIP events, pv_diagnostics() included
+        (mpas_dyc_get_profile out[13])."""
+        self._check(self.lib.mpas_dyc_set_profile(self.h, 1), "set_profile")
+        try:
+            self.pv_budget_diagnostics(time_level)
+        finally:
+            self._check(self.lib.mpas_dyc_set_profile(self.h, 0), "set_profile")
+        out = (C.c_double * 14)()
+        self._check(self.lib.mpas_dyc_get_profile(self.h, out, 14), "get_profile")
+        return float(out[13])
+
     def set_convective(self, flags: int | None = None, **outputs: bool):
         """Which outputs convective_diagnostics() computes (mpas_dyc_set_convective; the reference's
         MPAS_field_will_be_written switches, convective_diagnostics.F:285-312).  ``flags``: the
@@ -653,6 +700,7 @@ class Dycore:
             flags = T.scheme_flags(pbl, convection, lw, sw, rqvdynten)
         self._check(self.lib.mpas_dyc_set_todynamics(self.h, int(flags), int(index_qc), int(index_qr), int(index_qi),
                                                      int(index_qs), int(index_ni)), "set_todynamics")
+        self._todyn_flags = int(flags)  # set_pv_budget's default sources
         if not flags & (T.PBL | T.CU_WINDS):
             return
         for ib, c in enumerate(self.cases):  # the constructor leaves the PV diagnostics' mesh vectors to their hooks

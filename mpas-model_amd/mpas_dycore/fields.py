@@ -85,6 +85,15 @@ TODYN_MESH_INPUTS = ("east", "north")
 LOCATION.update({n: "cell" for n in TODYN_RAW + TODYN_MESH_INPUTS})
 LOCATION.update({n: "edge" for n in TODYN_EDGE})
 
+# the PV budget (mpas_dyc_set_pv_budget; diag pool): the eight terms and the two heating rates, one column per
+# cell (dtheta_dt_mp is the host's input), and the two terms on the 2-PVU surface, one value per cell
+PVB_OUTPUTS_3D = ("depv_dt_lw", "depv_dt_sw", "depv_dt_bl", "depv_dt_cu", "depv_dt_mp", "depv_dt_mix", "depv_dt_diab",
+                  "depv_dt_fric")
+PVB_HEATING = ("dtheta_dt_mp", "dtheta_dt_mix")
+PVB_OUTPUTS_2D = ("depv_dt_diab_pv", "depv_dt_fric_pv")
+PVB_FIELDS = PVB_OUTPUTS_3D + PVB_HEATING + PVB_OUTPUTS_2D
+LOCATION.update({n: "cell" for n in PVB_FIELDS})
+
 VERTICAL_1D = ("fzm", "fzp", "rdzw", "rdzu", "u_init", "v_init")
 SCALARS_0D = ("cf1", "cf2", "cf3")
 

@@ -17,9 +17,8 @@ One defined deviation: at level nVertLevels the reference forms dv_dz from velCe
 set there (:997).  Here, as on the device, that line takes velCellm, like the u line two above it.
 
 Arrays are element-major, 0-based: a field is (nCells, K); an index of -1 (no neighbour in the block)
-reads the garbage slot, which is never in the troposphere.  The PV budget (calc_pvBudget) and
-floodFill_strato are not restated: the first needs the physics suites' tendencies, the reference never
-calls the second.
+reads the garbage slot, which is never in the troposphere.  The PV budget (calc_pvBudget) is restated in
+mpas_dycore.pvbudget, on top of this module; floodFill_strato is not restated: the reference never calls it.
 """
 from __future__ import annotations
 
@@ -217,17 +216,20 @@ def interp_pv(ertel_pv, field1, ilev, lat, info: bool = False):
     return (out, inside & small) if info else out
 
 
-def driver(m: dict, f: dict, n_solve: int | None = None, ertel_pv_held=None) -> dict:
+def driver(m: dict, f: dict, n_solve: int | None = None, ertel_pv_held=None, theta_held=None) -> dict:
     """atm_compute_pv_diagnostics on one block without its halo exchanges.  m: the block's mesh arrays
     with cellTangentPlane, localVerticalUnitVectors, edgeNormalVectors, zgrid, zz.  f: theta_m, qv, rho_zz,
     w, uReconstructX/Y/Z, uReconstructZonal/Meridional (nCells, ...) and vorticity (nVertices, K) of the
     time level.  ertel_pv_held: what diag.ertel_pv holds on the cells past n_solve (default 0.0) -- the
-    fill reads it, as the reference's does after its exchange.  Returns theta, rho (nCells, K), ertel_pv
+    fill reads it, as the reference's does after its exchange.  theta_held: what diag.theta holds there after
+    its exchange (default: what the block computes from its own halo of theta_m and qv).  Returns theta, rho (nCells, K), ertel_pv
     (nCells, K), iLev_DT (nCells) and u_pv, v_pv, theta_pv, vort_pv (n_solve)."""
     n = int(m["nCells"])
     ns = n if n_solve is None else int(n_solve)
     theta, rho = theta_rho(np.asarray(f["theta_m"], dtype=np.float64), np.asarray(f["qv"], dtype=np.float64),
                            np.asarray(f["rho_zz"], dtype=np.float64), np.asarray(m["zz"], dtype=np.float64))
+    if theta_held is not None:
+        theta[ns:] = np.asarray(theta_held, dtype=np.float64)[ns:]
     g = geom(m, ns)
     K = theta.shape[1]
     pv = np.zeros((n, K)) if ertel_pv_held is None else np.array(ertel_pv_held, dtype=np.float64)
